@@ -17,10 +17,18 @@ ranks come from the environment (WORLD_SIZE must equal --gpus); a plain
 
 Printed by rank 0: one JSON line with the driver's contract fields plus
 `roofline` (montprog kernel: algorithmic integer MACs per second vs the
-half-rate v_mad_u64_u32 peak, per-launch HIP events on the engine stream) and
-`cpu_baseline` (the reference's own Paillier_GMP encrypt / decrypt / add /
-merge on the bench's key and inputs, OpenMP over bounded samples on this
-host's cores, cores and CPU model stated).
+half-rate v_mad_u64_u32 peak, per-launch HIP events on the engine stream of
+the timed steps themselves).
+
+A plain run does no more: set-up, warm-up, the timed steps, --dump-outputs,
+the line.  `--full` adds, after the timed steps, everything that takes runs
+of its own: `ciphertext_adds` (the metric's adds/s), `secondary` (decrypt,
+public and fixed-base encrypts, single-pair latencies, the drop-in's tools,
+P-1024, merges, histogram, host end-to-end, wire formats; the node-wide
+drop-in pass at N > 1), `cpu_baseline` (the reference's own Paillier_GMP
+encrypt / decrypt / add / merge on the bench's key and inputs, OpenMP over
+bounded samples on this host's cores, cores and CPU model stated) and the
+detail record (FTHE_BENCH_DETAIL).
 """
 import argparse
 import json
@@ -60,8 +68,16 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0: every core this process may use, see host_cpu())")
     ap.add_argument("--cpu-scale", type=float, default=1.0, help="CPU-baseline sample size multiplier")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the ciphertext adds/s, "
+                         "the secondary ops and drop-in tools, the CPU baseline, the node-wide pass at N > 1, and "
+                         "write the detail record (FTHE_BENCH_DETAIL).  Without it the run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(float64, a fixed seeded sample of the rows: see dump_outputs())")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary measurements")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank harness (launcher, barriers, max-over-ranks, "
                          "per-rank report): gloo, no GPU, a fixed sleep as the step; never a measurement")
@@ -465,6 +481,36 @@ def node_e2e(a, world, devices, rehearse):
     return out
 
 
+DUMP_ROWS = 32768    # sampled ciphertext rows of --dump-outputs: 32 MiB as float64 words (64 MB allowed in all)
+
+
+def dump_rows(total):
+    """The rows --dump-outputs keeps: all of them up to DUMP_ROWS, else a fixed sample (seeded by SEED, sorted,
+    without repeats), the same for every run with the same --pairs."""
+    if total <= DUMP_ROWS:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(total, DUMP_ROWS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, m, c):
+    """--dump-outputs DIR: what the last timed step left in HBM for its caller, as float64 .npy files (every value
+    is a 32-bit word, exact in float64), for output-by-output comparison of two builds run with the same arguments:
+      rows.npy         (R,)      the sampled row numbers (dump_rows)
+      ciphertexts.npy  (R, 128)  those rows of the step's ciphertexts, little-endian u32 words of c mod n^2
+      plaintexts.npy   (R, 2)    the fixed-point plaintexts the step's codec encoded for them (low, high u32 word)
+    Inputs, key and the device CSPRNG's seed of every step derive from SEED, the rank and the step number, so the
+    files are the same from run to run."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows = dump_rows(c.shape[0])
+    idx = torch.from_numpy(rows).to(c.device)
+    cs = c.index_select(0, idx).cpu().numpy().view(np.uint32)
+    ms = m.index_select(0, idx).cpu().numpy().view(np.uint32).reshape(len(rows), 2)
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "ciphertexts.npy"), cs.astype(np.float64))
+    np.save(os.path.join(path, "plaintexts.npy"), ms.astype(np.float64))
+
+
 def run(a, world):
     import torch
     import torch.distributed as dist
@@ -537,6 +583,8 @@ def run(a, world):
     busy, ebusy = ctypes.c_double(), ctypes.c_double()
     _lib.check(lib.fthe_prof_busy(dev.ctx, ctypes.byref(busy), ctypes.byref(ebusy)), "prof_busy")
     lib.fthe_prof_enable(dev.ctx, 0)
+    if a.dump_outputs and rank == 0:               # before --full's measurements reuse c
+        dump_outputs(a.dump_outputs, m, c)
     enc_rank = 2 * P * a.steps
     ident.update({"elapsed_s": round(elapsed_rank, 4), "encrypts_per_s": round(enc_rank / elapsed_rank, 1)})
     per_rank = gather_ranks(ident, world)
@@ -550,16 +598,18 @@ def run(a, world):
     # 8M adds per call (1M-add calls of ~1.4 ms disagreed by 10%); at most P, so the operands are always the two
     # distinct halves c[:na], c[na:2na] (x = y would read half the bytes and inflate the rate)
     na_rank = min(P, 1 << 23)
-    add_out = torch.empty((na_rank, 2 * pl.n_words), dtype=torch.int32, device=f"cuda:{local}")
-    add_b = c[na_rank:2 * na_rank]
+    adds = None
+    if a.full:                                     # runs of their own (6 add batches per rank): --full only
+        add_out = torch.empty((na_rank, 2 * pl.n_words), dtype=torch.int32, device=f"cuda:{local}")
+        add_b = c[na_rank:2 * na_rank]
 
-    def _add_call():
-        pl.add_dev(c[:na_rank], add_b, add_out)
-        dev.sync()
-        return lib.fthe_last_kernel_ms(dev.ctx) * 1e-3
+        def _add_call():
+            pl.add_dev(c[:na_rank], add_b, add_out)
+            dev.sync()
+            return lib.fthe_last_kernel_ms(dev.ctx) * 1e-3
 
-    adds = rank_adds(_add_call, na_rank, world, rank, sync)
-    del add_out, add_b
+        adds = rank_adds(_add_call, na_rank, world, rank, sync)
+        del add_out, add_b
 
     # -- roofline of the dominant kernel family (the exponentiation kernels, per-launch HIP
     # events on the engine stream, this rank).  Algorithmic work = the 32-bit MACs of the
@@ -672,7 +722,7 @@ def run(a, world):
 
     secondary = {}
     p1k_cpu = None
-    if rank == 0 and world == 1 and not a.no_secondary:      # N=1 runs only: scaling runs stay lean
+    if a.full and rank == 0 and world == 1 and not a.no_secondary:      # N=1 runs only: scaling runs stay lean
         # CRT decrypt of every ciphertext the step produced (configs[2]'s decrypt half: 20M at 10M pairs),
         # device-resident, one call
         nd = 2 * P
@@ -1177,14 +1227,14 @@ def run(a, world):
                 bytes(hb_[int(ho_[i]):int(ho_[i + 1])].numpy()).decode() for i in range(256)])})
         del ch, strs, back, fr, g_, dbuf, doffs, dback, hb_, ho_
     cpu = None
-    if rank == 0 and not a.no_cpu:                # after the timed region and its barrier, at every N
+    if a.full and rank == 0 and not a.no_cpu:     # after the timed region and its barrier, at every N
         ca = argparse.Namespace(**vars(a))
         if world > 1:
             ca.cpu_scale = a.cpu_scale / 4             # N > 1: a quarter sample keeps the scaling runs short
         cpu = cpu_baseline(ca, pl, p1k_cpu, m, c, dev)
         cpu["n_gpus_of_run"] = world
 
-    if rank == 0 and world > 1 and not a.no_secondary:
+    if a.full and rank == 0 and world > 1 and not a.no_secondary:
         # configs[4] through the class FedTree calls: Server::encrypt_gh_pairs / decrypt_gh_pairs on one
         # SyncArray<GHPair> of N x (pairs per device), Paillier_HIP sharding it over every device of the run in one
         # process (ShardPool: a worker thread, context and key replica per device, host rows in and out), in a
@@ -1195,7 +1245,7 @@ def run(a, world):
         line = {
             "metric": METRIC, "value": round(value, 1), "unit": "encrypts/s", "n_gpus": world,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "full": a.full,
             "data": "synthetic logistic gradients (splitmix64 seed 20261015+rank), fresh device-CSPRNG r per ciphertext",
             "config": {"workload": "Paillier-2048 encrypt of gradient pairs, device-resident, CRT (key holder)",
                        "pairs_per_gpu": P, "ciphertexts_per_gpu_per_step": 2 * P, "key_bits": KEY_BITS,
@@ -1208,7 +1258,8 @@ def run(a, world):
             line["rehearsal"] = "FTHE_BENCH_REHEARSE=1: all ranks on cuda:0 over gloo; not a measurement"
         if cpu:
             line["speedup_vs_cpu_baseline"] = round(value / cpu["value"], 1)
-        write_detail(line)
+        if a.full:
+            write_detail(line)
         print(compact_line(line), flush=True)
     if world > 1:
         dist.barrier(group=cpu_group)                  # the other ranks wait for rank 0's CPU stage (gloo: no GPU)

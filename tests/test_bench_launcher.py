@@ -118,6 +118,32 @@ def test_node_e2e_arguments_and_memory_cap(monkeypatch):
     assert cmd[4] == "0,0" and env["FTHE_SHIM_REPLICATE"] == "1"
 
 
+def test_dump_outputs_sample_is_fixed_and_exact(tmp_path):
+    """--dump-outputs: the same sorted, repeat-free rows for the same size (all rows of a small output), each u32
+    word of the sampled ciphertexts and plaintexts exact in float64, at most 64 MB for a full-size step."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    rows = bench.dump_rows(20_000_000)
+    assert len(rows) == bench.DUMP_ROWS and np.array_equal(rows, bench.dump_rows(20_000_000))
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 20_000_000
+    assert bench.DUMP_ROWS * (128 + 2 + 1) * 8 <= 64 * 10 ** 6
+    assert np.array_equal(bench.dump_rows(100), np.arange(100))
+    total = bench.DUMP_ROWS + 1000                     # one more than the cap: the sampled path, on CPU tensors
+    g = torch.Generator().manual_seed(1)
+    c = torch.randint(-2**31, 2**31 - 1, (total, 128), dtype=torch.int32, generator=g)
+    m = torch.randint(-2**62, 2**62, (total,), dtype=torch.int64, generator=g)
+    bench.dump_outputs(str(tmp_path / "d"), m, c)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("rows", "ciphertexts", "plaintexts")}
+    assert all(v.dtype == np.float64 for v in got.values())
+    idx = got["rows"].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_rows(total))
+    assert np.array_equal(got["ciphertexts"].astype(np.uint32), c.numpy().view(np.uint32)[idx])
+    lo_hi = got["plaintexts"].astype(np.uint64)
+    assert np.array_equal(lo_hi[:, 0] | (lo_hi[:, 1] << np.uint64(32)), m.numpy().view(np.uint64)[idx])
+
+
 def test_host_mem_bytes_is_positive():
     sys.path.insert(0, ROOT)
     import bench

@@ -17,7 +17,7 @@ def test_two_rank_rehearsal_prints_the_node_pass():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(FTHE_BENCH_REHEARSE="1", FTHE_BENCH_NODE_PAIRS="65536", FTHE_BENCH_DETAIL=os.devnull)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--pairs", "65536",
-                        "--steps", "1", "--warmup", "0", "--no-cpu"], capture_output=True, text=True, env=env,
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu"], capture_output=True, text=True, env=env,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

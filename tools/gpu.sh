@@ -5,7 +5,7 @@
 #   suite          python -m pytest tests -m gpu (thread timeouts: a hang names its test)
 #   test:FILE      python -m pytest FILE -m gpu (one test file, same timeouts)
 #   smoke          __graft_entry__.smoke()
-#   bench          python bench.py (the driver's default line)              -> TAG_bench.json
+#   bench          python bench.py --full (every measurement of the line)   -> TAG_bench.json
 #   bench:ARGS     python bench.py ARGS (comma-separated, e.g. bench:--steps,3)
 #   trace          the bench's timed region under rocprofv3 --kernel-trace --stats
 #   pmc:W          separate PMC passes (one counter group per run, never with tracing) over workload W:
@@ -17,7 +17,7 @@
 #                         (tools/nadicb_ab.py; the PMC summary separates the kernels by name)
 #                  then: python tools/rocprof_summary.py pmc gpurun_out/TAG_pmc_W_* out.json (CPU side)
 #   opstrace       kernel trace of tools/prof_ops.py add,kway (the add / merge launch durations for pmc:add)
-#   rehearse       FTHE_BENCH_REHEARSE=1 bench.py --gpus 2 (two ranks on the one GPU over gloo; ghpair_e2e_node
+#   rehearse       FTHE_BENCH_REHEARSE=1 bench.py --gpus 2 --full (two ranks on the one GPU over gloo; ghpair_e2e_node
 #                  over two contexts, NODE_PAIRS pairs per device, default 2M)
 #   ghpair         tools/bin/ghpair_rate twice at 16 threads (7 interleaved rounds each), tools/bin/ghpair_e2e
 #   marshal        tools/bin/marshal_rate: host mpz <-> row marshalling of 1, 2, 4, 8 concurrent shards (no kernels)
@@ -60,7 +60,7 @@ for step in "$@"; do
         || fail smoke $? ${O}_smoke.txt
       cat ${O}_smoke.txt;;
     bench)
-      timeout -k 10 900 python bench.py > ${O}_bench.json 2> ${O}_bench.err || fail bench $? ${O}_bench.err
+      timeout -k 10 900 python bench.py --full > ${O}_bench.json 2> ${O}_bench.err || fail bench $? ${O}_bench.err
       cut -c1-600 ${O}_bench.json;;
     bench:*)
       args=${step#bench:}
@@ -86,7 +86,7 @@ for step in "$@"; do
         python3 tools/prof_ops.py --n 1048576 --ops add,kway > ${O}_ops_trace.log 2>&1 || fail opstrace $? ${O}_ops_trace.log;;
     rehearse)
       FTHE_BENCH_REHEARSE=1 FTHE_BENCH_NODE_PAIRS=${NODE_PAIRS:-2000000} timeout -k 10 600 python bench.py --gpus 2 \
-        --pairs 1048576 --steps 2 --warmup 1 \
+        --pairs 1048576 --steps 2 --warmup 1 --full \
         > ${O}_rehearse_2rank_1gpu.json 2> ${O}_rehearse.err || fail rehearse $? ${O}_rehearse.err
       cut -c1-600 ${O}_rehearse_2rank_1gpu.json;;
     ghpair)
