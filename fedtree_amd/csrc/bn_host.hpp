@@ -84,7 +84,7 @@ struct MontMod {
         ctx.push_back(nprime);
         // MULWC (four-lane kernel): quotient-estimate constants, doubles -k1 = -2^32 invN,
         // -k2 = -2^27 invN, -k3 = -2^59 invN and bias, invN <= 2^(B(S-2)) / N (rounded down).
-        // Meaningful when N >= 2^(B S - 10) (classical_ok); zeros otherwise.
+        // Meaningful when N >= 2^(B S - 11) (classical_ok); zeros otherwise.
         double k[4] = {0, 0, 0, 0};
         if (classical_ok()) {
             Mpz t; mpz_fdiv_q_2exp(t, N, (mp_bitcnt_t)B * (S - 2) - 64);
@@ -100,7 +100,9 @@ struct MontMod {
         }
     }
     // the classical MSB-first product (OP_MULWC, tools/msb_model.py) needs the estimate's
-    // ignored columns below 2^-8 of a quotient unit: N >= 2^(B S - 10)
+    // ignored columns below 2^-8 of a quotient unit (the bias is 2^-6): N of at least B S - 10
+    // bits, i.e. N >= 2^(B S - 11) = 2^4093 for S = 152 (the argument: tools/msb_model.py;
+    // both ends of the range: tests/test_msb_model.py)
     bool classical_ok() const { return sh.lanes == 4 && mpz_sizeinbase(N, 2) >= (size_t)(B * S - 10); }
     std::vector<uint32_t> limbs(const mpz_t x) const { return to_limbs(x, S, B); }
     // x * R mod N (Montgomery form of x), as limbs
@@ -128,9 +130,9 @@ enum Op : uint32_t { OP_END = 0, OP_LOADX = 1, OP_STOREX = 2, OP_SQR = 3, OP_MUL
                      // the same with 16-bit windows (u16 digits, entry j*65536 + digit)
                      OP_LOADGD16 = 16, OP_MULGD16 = 17,
                      // four-lane kernel, row I/O: X <- row_t X mod N, classical MSB-first (no
-                     // Montgomery factor); X canonical, N >= 2^(B S - 10)
+                     // Montgomery factor); X canonical, N >= 2^(B S - 11)
                      OP_MULWC = 18,
-                     // the same with the gathered row of MULWG t; CANON: X (< 4N) -> X mod N
+                     // the same with the gathered row of MULWG t; CANON: X (any row, < 8N) -> X mod N
                      OP_MULWGC = 19, OP_CANON = 20,
                      // P-adic kernel (gen_padic.py): plain X (2K limbs) <-> base-P digits;
                      // its LOADX / STOREX / SQR / MUL move and multiply digits

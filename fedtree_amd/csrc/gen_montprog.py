@@ -931,7 +931,8 @@ def gen_quad(S: int, B: int, U: int, name: str) -> str:
     e('  s_branch .Lmontmul')
 
     # MULWC t: X <- row_t * X mod N, classical (no Montgomery factor): the pairwise add of two
-    # canonical ciphertexts in one product.  Needs X < N (canonical) and N >= 2^(B S - 10).
+    # canonical ciphertexts in one product.  Needs X < N (canonical) and N >= 2^(B S - 11) (2^4093 for
+    # S = 152: MontMod::classical_ok, tools/msb_model.py).
     e('.Lmulwc:')
     e('  s_lshr_b32 s19, s15, 8')                # arg bit 8: canonical output (chained products)
     e('  s_and_b32 s15, s15, 0xff')
@@ -951,17 +952,23 @@ def gen_quad(S: int, B: int, U: int, name: str) -> str:
     write_a(lambda j: f"v{A0 + j}")
     e('  s_branch .Lmontmul_msb')
 
-    # CANON: X (normalised limbs, < 4N: any 4096-bit row) -> X mod N, the precondition of MULWC
+    # CANON: X (normalised limbs, < 8N: any 4096-bit row, as N >= 2^4093) -> X mod N, the precondition
+    # of MULWC.  Seven compare-and-subtract rounds at most (a round leaves X < N unchanged); s15, the
+    # op's unused argument, counts them.
     e('.Lcanon:')
-    for r in range(3):
-        # skip the remaining rounds once every quad's top limb is below N's (then X < N):
-        # the case of every ciphertext (< n^2 <= N) after at most one round
-        e(f'  v_cmp_lt_u32_e32 vcc, {X(Q - 1)}, {NV(Q - 1)}')
-        e('  s_nop 4')
-        e('  s_and_b64 s[26:27], vcc, s[20:21]')
-        e('  s_cmp_eq_u64 s[26:27], s[20:21]')
-        e('  s_cbranch_scc1 .Lcanon_done')
-        canon_once(f'cn{r}')
+    e('  s_mov_b32 s15, 7')
+    e('.Lcanon_round:')
+    # skip the remaining rounds once every quad's top limb is below N's (then X < N):
+    # the case of every ciphertext (< n^2 <= N) after at most one round
+    e(f'  v_cmp_lt_u32_e32 vcc, {X(Q - 1)}, {NV(Q - 1)}')
+    e('  s_nop 4')
+    e('  s_and_b64 s[26:27], vcc, s[20:21]')
+    e('  s_cmp_eq_u64 s[26:27], s[20:21]')
+    e('  s_cbranch_scc1 .Lcanon_done')
+    canon_once('cn')
+    e('  s_sub_u32 s15, s15, 1')
+    e('  s_cmp_lg_u32 s15, 0')
+    e('  s_cbranch_scc1 .Lcanon_round')
     e('.Lcanon_done:')
     e('  s_branch .Lprog')
 

@@ -22,15 +22,21 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "fedtree_amd", "csrc"))
 
 import addb_model as am  # noqa: E402
+import n2_edges as ne  # noqa: E402
 
-KEYS = [None, (1 << 2047) + 1, (1 << 2048) - 1]
+# a random n, the synthetic ends of the range, and the prime-product edge keys (tests/golden/n2_edge_keys.json:
+# n just above 2^2047, just below 2^2048, n^2 on either side of 2^4095)
+KEYS = [None, (1 << 2047) + 1, (1 << 2048) - 1] + ne.ADDB_KEYS
 
 
 def _n(i):
+    if isinstance(KEYS[i], str):
+        p, q = ne.load_keys()[KEYS[i]]
+        return p * q
     return KEYS[i] if KEYS[i] else am.rand_n(random.Random(4))
 
 
-@pytest.mark.parametrize("ki", [0, 1, 2])
+@pytest.mark.parametrize("ki", range(len(KEYS)))
 def test_model_reduces_exactly(ki):
     n = _n(ki)
     k = am.AddbKey(n * n)
@@ -51,7 +57,7 @@ def test_model_rejects_short_moduli():
         am.AddbKey(((1 << 2046) + 1) ** 2)            # n of 2047 bits: N below 2^4094
 
 
-@pytest.mark.parametrize("ki", [0, 1, 2])
+@pytest.mark.parametrize("ki", range(len(KEYS)))
 def test_host_context_matches_model(ki):
     lib = ctypes.CDLL(os.path.join(ROOT, "fedtree_amd", "libfthe.so"))
     n = _n(ki)

@@ -14,6 +14,8 @@ r^n as prod hs_i^y_i with y_i uniform below 2^(16 nwin) >= n 2^64.  Checked here
 * injected exponents: bit-exact against (1 + m n) prod hs_i^y_i mod n^2 (Python
   pow) at the three golden key sizes (one-lane n^2 kernels at 512/1023 bits, the
   four-lane row form at 2048), incl. y = 0, 1 and the largest exponent covered;
+* the same against the reference's encrypt formula g^m r^n mod n^2 (the C oracle with r = prod t_i^y_i
+  injected, t_i the n-th roots of the published hs_i), party and key-holder public form;
 * device-drawn exponents: round trips, seeded determinism, fresh ciphertexts, the
   Server/Party histogram flow, known-order keys (2 bases);
 * refusals: no bases (public key: FTHE_ERR_NOPRIV), bad bases, bases without p, q.
@@ -122,6 +124,47 @@ def test_public_exact_injected_exponents(dev, name):
     # the key holder with the same bases, public form: identical ciphertexts
     server.set_public_bases(hs)
     assert np.array_equal(server.encrypt_u64(m, r=ys, public=True, fixed_base_exact=True), c)
+
+
+@pytest.mark.parametrize("name", GOLDEN_KEYS)
+def test_public_exact_equals_reference_encrypt(dev, coracle, name):
+    """The published-bases encrypt against the reference's own formula c = g^m r^n mod n^2
+    (paillier_gmp.cpp:37-73, restated with an injected r by the C oracle, which tests/test_oracle_golden.py pins
+    to the compiled reference): the key holder's t_i are recovered from the published hs_i as the n-th roots
+    t_i = (hs_i mod n)^d mod n, d = n^-1 mod lcm(p-1, q-1); then r = prod t_i^y_i mod n is the r of the
+    reference's encrypt, and the ciphertexts must agree bit for bit."""
+    from fedtree_amd.paillier import Paillier
+    p, q = golden_key(load_golden(name))
+    n = p * q
+    n2 = n * n
+    server = Paillier.from_primes(p, q, dev)
+    hs = server.public_bases(seed=7)
+    lam = (p - 1) * (q - 1) // math.gcd(p - 1, q - 1)
+    d = pow(n, -1, lam)
+    ts = [pow(h % n, d, n) for h in hs]
+    for t, h in zip(ts, hs):
+        assert pow(t, n, n2) == h                                # "hs_i is t_i^n"
+    nb, ebits = len(hs), hs.exp_bits[0]
+    rng = np.random.default_rng(len(name) + 500)
+    ys = [(0,) * nb, (1,) * nb, ((1 << ebits) - 1,) * nb, ((p - 1) * (q - 1), 0, 0)]
+    ys += [tuple(int.from_bytes(rng.bytes(ebits // 8), "little") for _ in range(nb)) for _ in range(12)]
+    m = rng.integers(0, 2**64, len(ys), dtype=np.uint64)
+    m[:3] = [0, 1, 2**64 - 1]
+    m[5:8] = [0, 1, 2**64 - 1]                                   # the same plaintexts under random exponents
+    rs = []
+    for y in ys:
+        r = 1
+        for t, e in zip(ts, y):
+            r = r * pow(t, e, n) % n
+        rs.append(r)
+    assert rs[0] == 1 and rs[3] == 1
+    hw = server.n_words // 2
+    ok = coracle.key(pyoracle.to_words(p, hw), pyoracle.to_words(q, hw))
+    want = ok.encrypt_batch(m, pyoracle.ints_to_words(rs, server.n_words))
+    party = server.public(bases=hs)
+    assert np.array_equal(party.encrypt_u64(m, r=ys, fixed_base_exact=True), want)
+    server.set_public_bases(hs)
+    assert np.array_equal(server.encrypt_u64(m, r=ys, public=True, fixed_base_exact=True), want)
 
 
 @pytest.mark.parametrize("name", ["ref_gmp_L2048.json", "ref_gmp_L4096.json"])

@@ -15,6 +15,18 @@ Step t (i = S-1-t, MSB first):
   5. column j -= q * N_j                          (v_mad_i64_i32 with -q)
 Invariant (checked here): 0 <= value < 2N after every step, |column| < 2^63, q < 2^29.
 The final signed normalisation + one conditional subtraction give X = A X mod N, canonical.
+
+Range of N: N >= 2^(B S - 11) = 2^4093 for S = 152 (MontMod::classical_ok).  The estimate reads the value
+down to position S-2 and ignores the columns below it.  Those are worth less than 2^-9 of one unit of q
+when N >= 2^4094 and the figure doubles each time N halves, so less than 2^-8 for N >= 2^4093; the double
+arithmetic (2^-53 relative on V, 2^-45 on invN, q < 2^29) adds less than 2^-15.  Both stay below the
+bias 2^-6, so q never exceeds the true quotient (value >= 0) and falls short of it by less than
+1 + 2^-5 (value < 2N).  Below 2^4093 the margin is not argued and the host does not use MULWC.
+Precondition: X < N (canonical; the kernel's CANON).  A may be any S-limb row.  The bound on q is where the
+precondition shows: q is about (previous value) 2^27 / N + a_i X / N < 2^28 + 2^27 for X < N, while a
+4096-bit X on N = 2^4093 + 1 (X ~ 8N) drives q to 31 bits, outside the stated invariant, even though
+the estimate still follows the value and the product comes out exact.
+tests/test_msb_model.py pins both ends of the range and the precondition.
 """
 import random
 import struct
@@ -73,10 +85,16 @@ def msb_mulmod(a, x, N, S, check=True):
             val = sum(c * BETA ** k for k, c in enumerate(col))
             assert 0 <= val < 2 * N, (t, val >= 0, val / N)
             assert all(-(1 << 63) < c < (1 << 63) for c in col)
+            assert q < 1 << 29, (t, q.bit_length())
     val = sum(c * BETA ** k for k, c in enumerate(col))
     if val >= N:
         val -= N
     return val, qmax
+
+
+# Bit lengths of the N that reach MULWC: MontMod::classical_ok (bn_host.hpp) admits N >= 2^(B S - 11) = 2^4093,
+# i.e. n^2 of a 2048-bit n (4095 or 4096 bits) and the upper half of the 2047-bit n (4094 bits).
+N_BITS = (4094, 4095, 4096)
 
 
 def main():
@@ -85,7 +103,7 @@ def main():
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 200
     qmax = 0
     for t in range(trials):
-        nb = rng.choice([4095, 4096, 4096, 4095])      # n^2 of a 2048-bit n: >= 2^4094 (MULWC is used only then)
+        nb = rng.choice(N_BITS)
         N = rng.getrandbits(nb) | (1 << (nb - 1)) | 1
         kind = t % 4
         if kind == 0:
