@@ -188,20 +188,6 @@ size_t rowio_chunk_lanes() {
     return v;
 }
 
-// Large CRT encrypts with device randomness pipelined across chunks: the p half of chunk i + 1 starts as soon as
-// the p half of chunk i has finished (the q half and the recombination of chunk i still running on the side
-// stream), so the chip never drains between chunks; two slot-region pairs alternate (15 GB more at P-2048).
-// Measured neutral (2.721 / 2.707M vs 2.729 / 2.706M encrypts/s, profiles/r05j_enc_pipe_ab.jsonl): the split
-// chunks already keep the chip full -- a chunk's p and q launches share it until the last round of waves -- so
-// it is opt-in, FTHE_ENC_PIPE=1 (bit-identical, tests/test_gpu_split_streams.py).
-bool enc_pipe() {
-    static const bool v = [] {
-        const char *e = getenv("FTHE_ENC_PIPE");
-        return e ? atoi(e) != 0 : false;
-    }();
-    return v;
-}
-
 // the key holder's large encrypt batches with device randomness (the direct-y path bench.py times) launch
 // twice chunk_lanes() per exponentiation: 786,432 lanes = six rounds of the P-adic kernel instead of three,
 // +1.5% encrypts/s (1.8% at 1,572,864; profiles/r04q_chunk_ab.jsonl); FTHE_ENC_CHUNK overrides
@@ -271,7 +257,13 @@ struct fthe_ctx {
     hipStream_t copy = nullptr;               // host<->device staging copies, overlapped with compute
     hipStream_t side = nullptr;               // second compute stream: the q half of small decrypts
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_cb[2] = {};                 // pipelined CRT encrypts: chunk i's recombination done (region i & 1)
+    // hand-offs between the main and the side stream: the side stream starts after what the main stream has
+    // queued; it marks its work done; the main stream goes on after that mark
+    int side_waits_main() {
+        HIPOK(hipEventRecord(ev_fork, stream)); HIPOK(hipStreamWaitEvent(side, ev_fork, 0)); return FTHE_OK;
+    }
+    int side_done() { HIPOK(hipEventRecord(ev_join, side)); return FTHE_OK; }
+    int main_waits_side() { HIPOK(hipStreamWaitEvent(stream, ev_join, 0)); return FTHE_OK; }
     int n_cu = 256;                           // compute units (small-batch spreading)
     int static_lds[MAX_VARIANTS] = {};        // per-variant static LDS bytes per workgroup
     PinBuf stage_out[2], stage_in[2];
@@ -567,7 +559,6 @@ extern "C" int fthe_ctx_create(int device, fthe_ctx **out) {
     HIPOK(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     HIPOK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     HIPOK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    for (auto &ev : c->ev_cb) HIPOK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     for (int i = 0; i < 2; i++) {
         HIPOK(hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming));
         HIPOK(hipEventCreateWithFlags(&c->ev_copied[i], hipEventDisableTiming));
@@ -628,7 +619,6 @@ extern "C" void fthe_ctx_destroy(fthe_ctx *c) {
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto &ev : c->ev_cb) if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < 2; i++) {
         if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
         if (c->ev_copied[i]) (void)hipEventDestroy(c->ev_copied[i]);
@@ -1603,6 +1593,7 @@ struct Launch {
     bool spread = false;           // one workgroup per CU (small concurrent launches)
     uint32_t *slot(int s) const { return (uint32_t *)base + (size_t)s * S * L; }
     dim3 grid() const { return dim3((unsigned)(L / 256)); }
+    hipStream_t stream() const { return st ? st : c->stream; }
     int prog(const fthe_key::PH &ph, const DevMod &mod, const void *const *rows = nullptr, int nrows = 0) {
         if (mod.m.S != S) return FTHE_ERR_ARG;
         int rc = launch_montprog(c, base, S, L, k->prog(ph), mod, ph.mm, live, rows, nrows, st, spread, ph.alg,
@@ -1619,7 +1610,7 @@ struct Launch {
         return FTHE_OK;
     }
     void fill(int s, int h) {
-        hipLaunchKernelGGL(k_fill_const, grid(), dim3(256), 0, st ? st : c->stream, k->cst(h), slot(s), S, L);
+        hipLaunchKernelGGL(k_fill_const, grid(), dim3(256), 0, stream(), k->cst(h), slot(s), S, L);
     }
 };
 
@@ -1631,7 +1622,7 @@ static int padic_launch(Launch &L, Launch *pa, const fthe_key *k, const fthe_key
     if (!k->padic_own_slots) return L.prog(ph, mA);
     Launch &A = *pa;
     A.live = L.live;
-    hipStream_t st = L.st ? L.st : L.c->stream;
+    hipStream_t st = L.stream();
     hipLaunchKernelGGL(k_copy_limbs, L.grid(), dim3(256), 0, st, L.slot(in), L.S, A.slot(in), A.S, L.L);
     if (int rc = A.prog(ph, mA)) return rc;
     L.mm += A.mm; A.mm = 0;
@@ -1654,20 +1645,37 @@ int dec_pow(Launch &L, const fthe_key *k, int side, Launch *pa = nullptr) {
         return rc;
     return L.prog(side ? k->prP_dec_post_q : k->prP_dec_post_p, m2);
 }
-// The P-adic region of a call on a key with padic_own_slots: c->slots1 after the stage-A region of
-// the small-limb kernel (sp1 slots of the same key, whose constants must survive across chunks).
-static size_t padic_region_offset(const fthe_key *k, int L) { return (size_t)nslots_for(k) * k->sp1.S * L * 4; }
-// paq (split calls): a second region after it for the q half on the side stream.
-static int padic_region(fthe_ctx *c, const fthe_key *k, const Launch &Lc, Launch &pa, Launch *paq = nullptr) {
-    pa = Lc;
-    if (paq) { *paq = Lc; paq->st = c->side; }
-    if (!k->padic_own_slots) return FTHE_OK;
-    pa.S = 2 * (k->mpA.kernel_S - 1000);
-    const size_t off = padic_region_offset(k, Lc.L), reg = (size_t)nslots_for(k) * pa.S * Lc.L * 4;
-    if (int rc = c->slots1.ensure(off + (paq ? 2 : 1) * reg)) return rc;
-    pa.base = (uint8_t *)c->slots1.p + off;
-    if (paq) { paq->S = pa.S; paq->base = (uint8_t *)pa.base + reg; }
-    return FTHE_OK;
+// The CRT recombination of an encrypt, c = c_q + q^2 h with h = (c_p - c_q) q^-2 mod p^2, in two steps around
+// the caller's p program (or pr_enc_tail, after a p program that stopped at c_p).  P owns the p slots, Q owns
+// SL_OUTQ: the same Launch unless the q half ran in a region of its own.  Both steps run on P's stream.
+static void crt_prep(Launch &P, const Launch &Q) {        // v = K - c_q into T0, after the q half
+    const fthe_key *k = P.k;
+    hipLaunchKernelGGL(k_crt_prep_q, P.grid(), dim3(256), 0, P.stream(), Q.slot(SL_OUTQ), k->cst(k->c_q2),
+                       k->cst(k->c_2p2), P.slot(SL_T0), P.S, P.L, P.B);
+}
+static void crt_out(Launch &P, const Launch &Q, size_t cnt, uint32_t *out) {   // h in T2 -> rows c (< p^2 q^2 = n^2)
+    const fthe_key *k = P.k;
+    const int S = P.S, cw = 2 * k->n_words;
+    hipLaunchKernelGGL(k_canon, P.grid(), dim3(256), 0, P.stream(), P.slot(SL_T2), k->cst(k->c_p2), S, P.L, P.B);
+    mul_add_out(P.stream(), P.grid(), Q.slot(SL_OUTQ), S, k->cst(k->c_q2), S, P.slot(SL_T2), S, P.L, cnt, out, cw,
+                (uint64_t *)nullptr, P.B);
+}
+
+// Constants of a region's exponentiation programs, for the halves it runs (the s80 set for a quad region).
+enum { kHalfP = 1, kHalfQ = 2, kBothHalves = 3 };
+// encrypt stage B: R^2 and n R per half, and Mont((q^2)^-1) for the CRT tail where both halves are
+static void fill_enc_consts(Launch &R, int halves, bool s80 = false) {
+    const fthe_key *k = R.k;
+    if (halves & kHalfP) { R.fill(SL_C0, s80 ? k->cl_R2p : k->c_R2p); R.fill(SL_C1, s80 ? k->cl_nRp : k->c_nRp); }
+    if (halves & kHalfQ) { R.fill(SL_C2, s80 ? k->cl_R2q : k->c_R2q); R.fill(SL_C3, s80 ? k->cl_nRq : k->c_nRq); }
+    if (halves == kBothHalves) R.fill(SL_T1, k->c_qinvRp2);
+}
+// decrypt: R^2 and R^3 per half, and Mont(1)
+static void fill_dec_consts(Launch &R, int halves, bool s80 = false) {
+    const fthe_key *k = R.k;
+    if (halves & kHalfP) { R.fill(SL_C0, s80 ? k->cl_R2p : k->c_R2p); R.fill(SL_C1, s80 ? k->cl_R3p : k->c_R3p); }
+    if (halves & kHalfQ) { R.fill(SL_C2, s80 ? k->cl_R2q : k->c_R2q); R.fill(SL_C3, s80 ? k->cl_R3q : k->c_R3q); }
+    R.fill(SL_T5, s80 ? k->cl_one : k->c_one);
 }
 
 int begin_call(fthe_ctx *c, const fthe_key *k, size_t count, Launch &Lc, int nslots, Shape sh,
@@ -1699,6 +1707,97 @@ int end_call(fthe_ctx *c, Launch &Lc) {
     c->last_mm = Lc.mm;
     if (hipGetLastError() != hipSuccess) return FTHE_ERR_HIP;
     return FTHE_OK;
+}
+
+// The form of a CRT decrypt or of an encrypt, and the memory of every region it runs in.
+//   quad:  at most dec_quad_max() rows of a key with the s80 shape: both halves on the four-lane kernel, each
+//          Montgomery product spread over a quad of lanes (~3x less latency per exponentiation), in two
+//          regions of slots1; the results go back to the s74 slots of main for the tail.  One chunk.
+//   split: the q half on the side stream beside the p half, in a second region of slots: calls of at most
+//          dec_split_lanes() lanes (one exponentiation of latency instead of two), and larger ones while
+//          split_all() is on (the finishing waves of one half overlap the other half).
+//   else:  the halves in turn on one stream, in one region.
+// Only calls with two independent halves have a choice: decrypts (but the short one, which has no q half, only
+// takes quad) and encrypts that draw y_p, y_q on the device (direct_y).
+struct CallNeed {
+    bool dec = false;           // decrypt (else encrypt)
+    bool crt = true;            // encrypt with the private key (else mod n^2)
+    bool direct_y = false;      // CRT encrypt drawing y_p, y_q: no stage A
+    bool short_pt = false;      // decrypt of plaintexts below p: the p half only
+    int rand_words = 0;         // u32 words of device-drawn randomness per row, kept in scratch
+};
+struct CallPlan {
+    bool quad = false, split = false;
+    Launch main;                // slots, main stream
+    Launch q;                   // split: the q half, region 2 of slots, side stream
+    Launch a;                   // explicit-r CRT encrypt: stage A mod p, q on the small-limb kernel (slots1)
+    Launch p4, q4;              // quad: the s80 regions of the p and q halves (slots1; q4 on the side stream)
+    Launch pa, paq;             // the P-adic kernel's own slots (Paillier-1024; else main's) of main and of q
+    uint32_t *rowp = nullptr, *rowq = nullptr;   // quad: canonical s80 rows on their way to main (scratch)
+    static constexpr int wl = (kLatShape.S * kLatShape.B + 31) / 32;   // u32 words of such a row
+};
+// The P-adic regions of a key with padic_own_slots lie in slots1 after the stage-A region of the small-limb
+// kernel (sp1 slots of the same key, whose constants must survive across chunks).
+static size_t padic_region_offset(const fthe_key *k, int L) { return (size_t)nslots_for(k) * k->sp1.S * L * 4; }
+// Every buffer of the call is sized here, once, before any pointer is carved from it: no DevBuf is ensure()d
+// after that in the same call (ensure may free and reallocate).
+static int plan_call(fthe_ctx *c, const fthe_key *k, size_t count, const CallNeed &need, CallPlan &pl) {
+    const int vi = variant_index(k->spq.S);
+    const bool halves = need.dec || need.direct_y;
+    // (one chunk by construction: FTHE_CHUNK below the quad limit sends the batch down the other forms)
+    pl.quad = halves && k->slat.S && count > 0 && count <= dec_quad_max() && count <= chunk_lanes();
+    const bool can_split = !pl.quad && halves && !need.short_pt && vi >= 0;
+    const bool small_split = can_split && count * (size_t)kVariants[vi].lanes <= dec_split_lanes();
+    pl.split = can_split && (small_split || split_all());
+    const int nsl = nslots_for(k);
+    Launch &Lc = pl.main;
+    auto begin = [&] {
+        return begin_call(c, k, count, Lc, pl.split ? 2 * nsl : nsl, need.crt ? k->spq : k->sn2,
+                          need.direct_y && !small_split && !pl.quad ? enc_chunk_lanes()
+                          : !need.crt && k->nadic_b                 ? pub_chunk_lanes() : 0);
+    };
+    int rc = begin();
+    // the second region of a large call is a speed option (+1%): when the device (or the context's limit,
+    // fthe_ctx_set_mem_limit) cannot hold it, the call takes the one-region form, bit-identical
+    if (rc == FTHE_ERR_NOMEM && pl.split && !small_split) {
+        pl.split = false;
+        rc = begin();
+    }
+    if (rc) return rc;
+    const size_t L = (size_t)Lc.L;
+    if (pl.quad && count > L) return FTHE_ERR_ARG;             // one chunk by construction
+    const bool stage_a = !need.dec && need.crt && !need.direct_y;
+    // (a key with the s80 shape has s74 slots, which the P-adic kernel shares: no quad call has regions of it)
+    const int npa = k->padic_own_slots && need.crt && !pl.quad ? (pl.split ? 2 : 1) : 0;
+    const int Spa = npa ? 2 * (k->mpA.kernel_S - 1000) : 0;
+    const size_t reg4 = (size_t)nsl * kLatShape.S * L * 4, off = padic_region_offset(k, (int)L),
+                 regpa = (size_t)nsl * Spa * L * 4;
+    if ((rc = c->slots1.ensure(pl.quad ? 2 * reg4 : stage_a || npa ? off + npa * regpa : (size_t)0))) return rc;
+    const size_t yrow = need.direct_y ? 2 * (size_t)k->pq_w : 0;       // quad: the rows follow y_p, y_q
+    if ((rc = c->scratch.ensure(std::max(L * need.rand_words * 4, pl.quad ? L * (yrow + 2 * pl.wl) * 4 : (size_t)0))))
+        return rc;
+    pl.a = Lc;
+    pl.a.S = k->sp1.S; pl.a.B = k->sp1.B; pl.a.base = c->slots1.p;
+    pl.p4 = Lc;
+    pl.p4.S = kLatShape.S; pl.p4.B = kLatShape.B; pl.p4.base = c->slots1.p; pl.p4.spread = !need.short_pt;
+    pl.q4 = pl.p4; pl.q4.base = (uint8_t *)c->slots1.p + reg4; pl.q4.st = c->side;
+    pl.rowp = (uint32_t *)c->scratch.p + L * yrow; pl.rowq = pl.rowp + L * pl.wl;
+    if (pl.split) Lc.spread = true;
+    pl.q = Lc;
+    if (pl.split) { pl.q.base = (uint8_t *)Lc.base + (size_t)nsl * Lc.S * L * 4; pl.q.st = c->side; }
+    pl.pa = Lc; pl.paq = pl.q;
+    if (npa) {
+        pl.pa.S = pl.paq.S = Spa;
+        pl.pa.base = (uint8_t *)c->slots1.p + off;
+        pl.paq.base = (uint8_t *)pl.pa.base + regpa;
+    }
+    return FTHE_OK;
+}
+// quad hand-back: the canonical rows of an s80 slot (mod the constant P2) -> the same slot of main
+static void quad_hand_back(CallPlan &pl, const Launch &L4, int slot, int P2, size_t cnt, uint32_t *rows) {
+    Launch &Lc = pl.main;
+    unpack_rows(Lc.c->stream, L4.slot(slot), Lc.k->cst(P2), L4.S, L4.L, cnt, rows, pl.wl, L4.B);
+    pack_rows(Lc.c->stream, rows, pl.wl, cnt, 0, Lc.slot(slot), Lc.S, Lc.L, Lc.B);
 }
 
 // Host-resident calls: chunked, double-buffered transfers through pinned
@@ -1885,6 +1984,61 @@ static int encrypt_xb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, con
                            int y_words, uint64_t rng_seed, uint32_t *out, HostPipe *pipe);
 static int encrypt_pb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const uint32_t *y, int y_words,
                            uint64_t rng_seed, uint32_t *out, HostPipe *pipe);
+// One chunk of the direct-y CRT encrypt: y_p, y_q drawn into scratch, the two stage-B exponentiations in the
+// plan's form, the recombination into out.
+static int enc_direct_y_chunk(CallPlan &pl, const MsgSrc &m, const RngKey &rk, size_t off, size_t cnt, uint32_t *out) {
+    Launch &Lc = pl.main, &Lq = pl.q;
+    fthe_ctx *c = Lc.c;
+    const fthe_key *k = Lc.k;
+    const int S = Lc.S, L = Lc.L;
+    int rc;
+    uint32_t *yp = (uint32_t *)c->scratch.p, *yq = yp + (size_t)L * k->pq_w;
+    RngKey rq = rk; rq.nonce ^= kYqStream;                    // an independent stream for y_q
+    hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_pqwords, k->pq_w, (int)k->p.bits(), rk,
+                       m.idx0 + off, cnt, yp);
+    hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_pqwords + k->pq_w, k->pq_w,
+                       (int)k->q.bits(), rq, m.idx0 + off, cnt, yq);
+    m.pack(c->stream, Lc.grid(), off, cnt, Lc.slot(SL_IN1), S, L, Lc.B);
+    pack_rows(c->stream, yp, k->pq_w, cnt, 0, Lc.slot(SL_T3), S, L, Lc.B);
+    pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lc.slot(SL_T4), S, L, Lc.B);
+    if (pl.quad) {
+        Launch &Lp4 = pl.p4, &Lq4 = pl.q4;
+        const int S4 = Lp4.S, B4 = Lp4.B;
+        Lp4.live = cnt; Lq4.live = cnt;
+        m.pack(c->stream, Lc.grid(), off, cnt, Lp4.slot(SL_IN1), S4, L, B4);
+        m.pack(c->stream, Lc.grid(), off, cnt, Lq4.slot(SL_IN1), S4, L, B4);
+        pack_rows(c->stream, yp, k->pq_w, cnt, 0, Lp4.slot(SL_T3), S4, L, B4);
+        pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lq4.slot(SL_T4), S4, L, B4);
+        if ((rc = c->side_waits_main())) return rc;
+        if ((rc = Lq4.prog(k->pr_enc_ql, k->mq2l))) return rc;
+        if ((rc = c->side_done())) return rc;
+        if ((rc = Lp4.prog(k->pr_enc_pl, k->mp2l))) return rc;
+        // canonical c_p, c_q rows -> the s74 slots of the CRT tail
+        quad_hand_back(pl, Lp4, SL_OUTP, k->cl_p2, cnt, pl.rowp);
+        if ((rc = c->main_waits_side())) return rc;
+        quad_hand_back(pl, Lq4, SL_OUTQ, k->cl_q2, cnt, pl.rowq);
+        Lc.mm += Lp4.mm + Lq4.mm; Lp4.mm = Lq4.mm = 0;
+        crt_prep(Lc, Lc);
+        if ((rc = Lc.prog(k->pr_enc_tail, k->mp2))) return rc;
+    } else if (pl.split) {
+        m.pack(c->stream, Lc.grid(), off, cnt, Lq.slot(SL_IN1), S, L, Lc.B);
+        pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lq.slot(SL_T4), S, L, Lc.B);
+        if ((rc = c->side_waits_main())) return rc;
+        if ((rc = enc_stage_b(Lq, k, 1, false, &pl.paq))) return rc;
+        if ((rc = c->side_done())) return rc;
+        if ((rc = enc_stage_b(Lc, k, 0, true, &pl.pa))) return rc;
+        if ((rc = c->main_waits_side())) return rc;
+        crt_prep(Lc, Lq);
+        if ((rc = Lc.prog(k->pr_enc_tail, k->mp2))) return rc;
+    } else {
+        if ((rc = enc_stage_b(Lc, k, 1, false, &pl.pa))) return rc;
+        crt_prep(Lc, Lc);
+        if ((rc = enc_stage_b(Lc, k, 0, false, &pl.pa))) return rc;                 // ends with h = (cp - cq) q^-2 in T2
+    }
+    crt_out(Lc, pl.split ? Lq : Lc, cnt, out);
+    return FTHE_OK;
+}
+
 static int encrypt_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const uint32_t *r, int r_words,
                         uint64_t rng_seed, uint32_t *out, int flags, HostPipe *pipe) {
     if (!k || !c || (m.null() && count) || (!out && count)) return FTHE_ERR_ARG;
@@ -1901,214 +2055,51 @@ static int encrypt_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const 
     }
     if (!crt && !k->pub_ok) return FTHE_ERR_UNSUPPORTED;
     if (flags & FTHE_ENC_FIXED_BASE) return encrypt_fb_impl(k, c, m, count, r, r_words, rng_seed, out, crt, pipe);
-    static const bool no_direct = getenv("FTHE_NO_DIRECT_Y") != nullptr;
-    const bool direct_y = crt && !r && !no_direct;
-    // small batches: the q half on the side stream in a second slot region, as decrypt_impl
-    const int vi = variant_index(k->spq.S);
-    // and smaller ones both halves on the four-lane s80 kernel (as decrypt_impl)
-    // (one chunk by construction: FTHE_CHUNK below the quad limit sends the batch down the other paths)
-    const bool quad = direct_y && k->slat.S && count > 0 && count <= dec_quad_max() && count <= chunk_lanes();
-    const bool small_split = !quad && direct_y && vi >= 0 && count * (size_t)kVariants[vi].lanes <= dec_split_lanes();
-    bool big_split = !quad && !small_split && direct_y && vi >= 0 && split_all();
-    // big split calls of more than one chunk: chunks pipelined over two slot-region pairs (enc_pipe)
-    bool piped = big_split && !pipe && !k->padic_own_slots && enc_pipe() && count > enc_chunk_lanes();
-    const int nsl = nslots_for(k);
-    Launch Lc;
-    auto begin = [&] {
-        return begin_call(c, k, count, Lc, piped ? 4 * nsl : (small_split || big_split) ? 2 * nsl : nsl,
-                          crt ? k->spq : k->sn2,
-                          direct_y && !small_split && !quad ? enc_chunk_lanes() : !crt && k->nadic_b ? pub_chunk_lanes() : 0);
-    };
-    int rc = begin();
-    // the extra regions of the pipelined / two-stream forms are a speed option (+1%): when the device (or the
-    // context's limit, fthe_ctx_set_mem_limit) cannot hold them, the call takes the one-region form, bit-identical
-    while (rc == FTHE_ERR_NOMEM && (piped || big_split)) {
-        if (piped) piped = false; else big_split = false;
-        rc = begin();
-    }
-    const bool split = small_split || big_split;
-    if (rc) return rc;
-    const int S = Lc.S, L = Lc.L, nw = k->n_words, cw = 2 * nw;
     // Device-drawn randomness under CRT draws y_p, y_q uniform in [1,p), [1,q) and
     // skips stage A: r^n mod P^2 = (r^Q mod P)^P and r -> r^Q mod P is a bijection of
     // Z_P^* (gcd(n, phi(n)) = 1, checked at key set-up as paillier.cpp:60), so
     // y^P mod P^2 for uniform y has exactly the distribution of r^n mod P^2 for the
     // reference's uniform r, independently for P = p, q (CRT).  FTHE_NO_DIRECT_Y=1
     // keeps the explicit r (A/B).  Injected r always takes both stages (bit-exact).
-    // scratch: AoS r words for the device RNG
-    const int wl = (kLatShape.S * kLatShape.B + 31) / 32;   // u32 words of an s80 row
-    if (!r && (rc = c->scratch.ensure(std::max((size_t)L * nw * 4 * (direct_y ? 2 : 1) * (piped ? 2 : 1),
-                                               quad ? (size_t)L * (2 * k->pq_w + 2 * wl) * 4 : (size_t)0))))
-        return rc;
+    static const bool no_direct = getenv("FTHE_NO_DIRECT_Y") != nullptr;
+    const bool direct_y = crt && !r && !no_direct;
+    const int nw = k->n_words, cw = 2 * nw;
+    CallNeed need;
+    need.crt = crt; need.direct_y = direct_y;
+    need.rand_words = r ? 0 : direct_y ? 2 * nw : nw;          // AoS r (or y_p, y_q) words for the device RNG
+    CallPlan pl;
+    int rc = plan_call(c, k, count, need, pl);
+    if (rc) return rc;
+    Launch &Lc = pl.main, &L1 = pl.a;
+    const int S = Lc.S, L = Lc.L;
     RngKey rk{};
     if (!r) rk = make_rng_key(rng_seed, 0);
-    Launch L1 = Lc;                    // stage A: mod p, q on the small-limb kernel, own slot region
-    Launch Lq = Lc;                    // split: q half, region 2 of the slots, side stream
-    if (split) {
-        Lq.base = (uint8_t *)Lc.base + (size_t)nsl * S * L * 4;
-        Lq.st = c->side;
-        Lc.spread = Lq.spread = true;
-        HIPOK(hipEventRecord(c->ev_fork, c->stream));
-        HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        Lq.fill(SL_C2, k->c_R2q); Lq.fill(SL_C3, k->c_nRq);
+    if (pl.split) {
+        if ((rc = c->side_waits_main())) return rc;
+        fill_enc_consts(pl.q, kHalfQ);
     }
-    Launch Lp4 = Lc, Lq4 = Lc;         // quad: s80 regions for the p and q halves (slots1)
-    if (quad) {
-        if (count > (size_t)L) return FTHE_ERR_ARG;        // one chunk by construction
-        const size_t reg = (size_t)nsl * kLatShape.S * L * 4;
-        if ((rc = c->slots1.ensure(2 * reg))) return rc;
-        Lp4.S = kLatShape.S; Lp4.B = kLatShape.B; Lp4.base = c->slots1.p; Lp4.spread = true;
-        Lq4 = Lp4; Lq4.base = (uint8_t *)c->slots1.p + reg; Lq4.st = c->side;
-        Lp4.fill(SL_C0, k->cl_R2p); Lp4.fill(SL_C1, k->cl_nRp);
-        Lq4.fill(SL_C2, k->cl_R2q); Lq4.fill(SL_C3, k->cl_nRq);
-    }
-    Launch Lpa, Lpaq;                  // the P-adic kernel's own slots (Paillier-1024; else Lc's)
-    if (crt && (rc = padic_region(c, k, Lc, Lpa, split ? &Lpaq : nullptr))) return rc;
-    if (direct_y) {
-        Lc.fill(SL_C0, k->c_R2p); Lc.fill(SL_C1, k->c_nRp);
-        Lc.fill(SL_C2, k->c_R2q); Lc.fill(SL_C3, k->c_nRq);
-        Lc.fill(SL_T1, k->c_qinvRp2);
-    } else if (crt) {
-        L1.S = k->sp1.S; L1.B = k->sp1.B;
-        if ((rc = c->slots1.ensure(std::max((size_t)nslots_for(k) * L1.S * L * 4,
-                                            k->padic_own_slots ? padic_region_offset(k, L) +
-                                                (size_t)nslots_for(k) * Lpa.S * L * 4 : (size_t)0))))
-            return rc;
-        L1.base = c->slots1.p;                 // stage A; the P-adic region (if any) follows it
-        if (k->padic_own_slots) Lpa.base = (uint8_t *)c->slots1.p + padic_region_offset(k, L);
+    if (pl.quad) { fill_enc_consts(pl.p4, kHalfP, true); fill_enc_consts(pl.q4, kHalfQ, true); }
+    if (crt && !direct_y) {
         L1.fill(SL_C0, k->c1_R2p); L1.fill(SL_C1, k->c1_R3p);
         L1.fill(SL_C2, k->c1_R2q); L1.fill(SL_C3, k->c1_R3q);
         L1.fill(SL_T5, k->c1_one);
-        Lc.fill(SL_C0, k->c_R2p); Lc.fill(SL_C1, k->c_nRp);
-        Lc.fill(SL_C2, k->c_R2q); Lc.fill(SL_C3, k->c_nRq);
-        Lc.fill(SL_T1, k->c_qinvRp2);
+    }
+    if (crt) {
+        fill_enc_consts(Lc, kBothHalves);
     } else {
         Lc.fill(SL_C0, k->c_R2n2); Lc.fill(SL_C1, k->c_nRn2);
     }
-    if (piped) {
-        // region pair b = chunk & 1: the p half (main stream) on Rp[b], the q half and the recombination (side
-        // stream) on Rq[b].  Chunk i's p half waits only for the recombination of chunk i - 2 (the last user of
-        // its region pair and of its y buffers), so it runs beside the q half of chunk i - 1.
-        Launch Rp[2] = {Lc, Lc}, Rq[2] = {Lq, Lq};
-        Rp[1].base = (uint8_t *)Lc.base + (size_t)2 * nsl * S * L * 4;
-        Rq[1].base = (uint8_t *)Lc.base + (size_t)3 * nsl * S * L * 4;
-        Rp[1].fill(SL_C0, k->c_R2p); Rp[1].fill(SL_C1, k->c_nRp);
-        Rp[1].fill(SL_C2, k->c_R2q); Rp[1].fill(SL_C3, k->c_nRq);
-        Rp[1].fill(SL_T1, k->c_qinvRp2);
-        Rq[1].fill(SL_C2, k->c_R2q); Rq[1].fill(SL_C3, k->c_nRq);
-        double mm_tail = 0;
-        size_t i = 0;
-        for (size_t off = 0; off < count; off += L, i++) {
-            const int b = (int)(i & 1);
-            const size_t cnt = std::min((size_t)L, count - off);
-            Launch &P = Rp[b], &Q = Rq[b];
-            P.live = Q.live = cnt;
-            uint32_t *yp = (uint32_t *)c->scratch.p + (size_t)b * 2 * L * k->pq_w, *yq = yp + (size_t)L * k->pq_w;
-            RngKey rq = rk; rq.nonce ^= kYqStream;
-            if (i >= 2) HIPOK(hipStreamWaitEvent(c->stream, c->ev_cb[b], 0));
-            hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_pqwords, k->pq_w, (int)k->p.bits(),
-                               rk, m.idx0 + off, cnt, yp);
-            m.pack(c->stream, Lc.grid(), off, cnt, P.slot(SL_IN1), S, L, Lc.B);
-            pack_rows(c->stream, yp, k->pq_w, cnt, 0, P.slot(SL_T3), S, L, Lc.B);
-            if ((rc = enc_stage_b(P, k, 0, true, &Lpa))) return rc;
-            HIPOK(hipEventRecord(c->ev_fork, c->stream));
-            hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->side, k->d_pqwords + k->pq_w, k->pq_w,
-                               (int)k->q.bits(), rq, m.idx0 + off, cnt, yq);
-            m.pack(c->side, Lc.grid(), off, cnt, Q.slot(SL_IN1), S, L, Lc.B);
-            pack_rows(c->side, yq, k->pq_w, cnt, 0, Q.slot(SL_T4), S, L, Lc.B);
-            if ((rc = enc_stage_b(Q, k, 1, false, &Lpaq))) return rc;
-            HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-            Launch T = P;                  // the recombination: P's slots, on the side stream
-            T.st = c->side; T.mm = 0;
-            hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->side, Q.slot(SL_OUTQ), k->cst(k->c_q2),
-                               k->cst(k->c_2p2), P.slot(SL_T0), S, L, Lc.B);
-            if ((rc = T.prog(k->pr_enc_tail, k->mp2))) return rc;
-            mm_tail += T.mm;
-            hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->side, P.slot(SL_T2), k->cst(k->c_p2), S, L, Lc.B);
-            mul_add_out(c->side, Lc.grid(), Q.slot(SL_OUTQ), S, k->cst(k->c_q2), S, P.slot(SL_T2), S, L, cnt,
-                        out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
-            HIPOK(hipEventRecord(c->ev_cb[b], c->side));
-        }
-        HIPOK(hipEventRecord(c->ev_join, c->side));
-        HIPOK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        Lc.mm = Rp[0].mm + Rp[1].mm + Rq[0].mm + Rq[1].mm + mm_tail;
-        return end_call(c, Lc);
-    }
     for (size_t off = 0; off < count; off += L) {
         size_t cnt = std::min((size_t)L, count - off);
-        Lc.live = cnt; L1.live = cnt; Lq.live = cnt;
+        Lc.live = cnt; L1.live = cnt; pl.q.live = cnt;
         if (pipe && (rc = pipe->before(off, L, count))) return rc;
-        const uint32_t *rw = r + (r ? off * r_words : 0);
-        int rwn = r_words;
         if (direct_y) {
-            uint32_t *yp = (uint32_t *)c->scratch.p, *yq = yp + (size_t)L * k->pq_w;
-            RngKey rq = rk; rq.nonce ^= kYqStream;                    // an independent stream for y_q
-            hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_pqwords, k->pq_w, (int)k->p.bits(),
-                               rk, m.idx0 + off, cnt, yp);
-            hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_pqwords + k->pq_w, k->pq_w,
-                               (int)k->q.bits(), rq, m.idx0 + off, cnt, yq);
-            m.pack(c->stream, Lc.grid(), off, cnt, Lc.slot(SL_IN1), S, L, Lc.B);
-            pack_rows(c->stream, yp, k->pq_w, cnt, 0, Lc.slot(SL_T3), S, L, Lc.B);
-            pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lc.slot(SL_T4), S, L, Lc.B);
-            if (quad) {
-                const int S4 = kLatShape.S, B4 = kLatShape.B;
-                uint32_t *rowp = yq + (size_t)L * k->pq_w, *rowq = rowp + (size_t)L * wl;
-                Lp4.live = cnt; Lq4.live = cnt;
-                m.pack(c->stream, Lc.grid(), off, cnt, Lp4.slot(SL_IN1), S4, L, B4);
-                m.pack(c->stream, Lc.grid(), off, cnt, Lq4.slot(SL_IN1), S4, L, B4);
-                pack_rows(c->stream, yp, k->pq_w, cnt, 0, Lp4.slot(SL_T3), S4, L, B4);
-                pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lq4.slot(SL_T4), S4, L, B4);
-                HIPOK(hipEventRecord(c->ev_fork, c->stream));
-                HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                if ((rc = Lq4.prog(k->pr_enc_ql, k->mq2l))) return rc;
-                HIPOK(hipEventRecord(c->ev_join, c->side));
-                if ((rc = Lp4.prog(k->pr_enc_pl, k->mp2l))) return rc;
-                // canonical c_p, c_q rows -> the s74 slots of the CRT tail
-                unpack_rows(c->stream, Lp4.slot(SL_OUTP), k->cst(k->cl_p2), S4, L, cnt, rowp, wl, B4);
-                pack_rows(c->stream, rowp, wl, cnt, 0, Lc.slot(SL_OUTP), S, L, Lc.B);
-                HIPOK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                unpack_rows(c->stream, Lq4.slot(SL_OUTQ), k->cst(k->cl_q2), S4, L, cnt, rowq, wl, B4);
-                pack_rows(c->stream, rowq, wl, cnt, 0, Lc.slot(SL_OUTQ), S, L, Lc.B);
-                Lc.mm += Lp4.mm + Lq4.mm; Lp4.mm = Lq4.mm = 0;
-                hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTQ),
-                                   k->cst(k->c_q2), k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
-                if ((rc = Lc.prog(k->pr_enc_tail, k->mp2))) return rc;
-                hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S,
-                                   L, Lc.B);
-                mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S, k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt,
-                            out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
-                if (pipe && (rc = pipe->after(off, cnt))) return rc;
-                continue;
-            }
-            if (split) {
-                m.pack(c->stream, Lc.grid(), off, cnt, Lq.slot(SL_IN1), S, L, Lc.B);
-                pack_rows(c->stream, yq, k->pq_w, cnt, 0, Lq.slot(SL_T4), S, L, Lc.B);
-                HIPOK(hipEventRecord(c->ev_fork, c->stream));
-                HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                if ((rc = enc_stage_b(Lq, k, 1, false, &Lpaq))) return rc;
-                HIPOK(hipEventRecord(c->ev_join, c->side));
-                if ((rc = enc_stage_b(Lc, k, 0, true, &Lpa))) return rc;
-                HIPOK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lq.slot(SL_OUTQ),
-                                   k->cst(k->c_q2), k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
-                if ((rc = Lc.prog(k->pr_enc_tail, k->mp2))) return rc;
-                hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S,
-                                   L, Lc.B);
-                mul_add_out(c->stream, Lc.grid(), Lq.slot(SL_OUTQ), S, k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt,
-                            out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
-                if (pipe && (rc = pipe->after(off, cnt))) return rc;
-                continue;
-            }
-            if ((rc = enc_stage_b(Lc, k, 1, false, &Lpa))) return rc;
-            hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTQ), k->cst(k->c_q2),
-                               k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
-            if ((rc = enc_stage_b(Lc, k, 0, false, &Lpa))) return rc;                 // ends with h = (cp - cq) q^-2 in T2
-            hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S, L, Lc.B);
-            mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S,
-                        k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt, out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
+            if ((rc = enc_direct_y_chunk(pl, m, rk, off, cnt, out + off * cw))) return rc;
             if (pipe && (rc = pipe->after(off, cnt))) return rc;
             continue;
         }
+        const uint32_t *rw = r + (r ? off * r_words : 0);
+        int rwn = r_words;
         if (!r) {
             hipLaunchKernelGGL(k_rng_r, Lc.grid(), dim3(256), 0, c->stream, k->d_nwords, nw, k->n_bits, rk,
                                m.idx0 + off, cnt, (uint32_t *)c->scratch.p);
@@ -2128,14 +2119,10 @@ static int encrypt_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const 
                                Lc.slot(SL_T3), S, L);
             hipLaunchKernelGGL(k_copy_limbs, Lc.grid(), dim3(256), 0, c->stream, L1.slot(SL_OUTQ), L1.S,
                                Lc.slot(SL_T4), S, L);
-            if ((rc = enc_stage_b(Lc, k, 1, false, &Lpa))) return rc;
-            hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTQ), k->cst(k->c_q2),
-                               k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
-            if ((rc = enc_stage_b(Lc, k, 0, false, &Lpa))) return rc;                 // ends with h = (cp - cq) q^-2 in T2
-            hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S, L, Lc.B);
-            // c = cq + q^2 h   (< p^2 q^2 = n^2)
-            mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S,
-                        k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt, out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
+            if ((rc = enc_stage_b(Lc, k, 1, false, &pl.pa))) return rc;
+            crt_prep(Lc, Lc);
+            if ((rc = enc_stage_b(Lc, k, 0, false, &pl.pa))) return rc;                 // ends with h = (cp - cq) q^-2 in T2
+            crt_out(Lc, Lc, cnt, out + off * cw);
         } else if (k->nadic || k->nadic_mont || k->nadic_b) {
             // n-adic kernel: digits (r, 0) in IN0, (1, m) in C1; out = x0 + x1 n (x0, x1 < n: c < n^2)
             const int D = kNadicDigit.S;
@@ -2168,7 +2155,7 @@ static int encrypt_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const 
         Lc.mm += L1.mm; L1.mm = 0;
         if (pipe && (rc = pipe->after(off, cnt))) return rc;
     }
-    Lc.mm += Lq.mm;
+    Lc.mm += pl.q.mm;
     return end_call(c, Lc);
 }
 
@@ -2510,12 +2497,9 @@ static int encrypt_fb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, con
             const void *rp[2] = {F.d_tab_p, dig_p};
             const void *rq[2] = {F.d_tab_q, sides == 2 ? dig_q : dig_p};
             if ((rc = Lc.prog_raw(prog + F.off_q, F.mm_crt, k->mq2, rq, 2))) return rc;
-            hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTQ), k->cst(k->c_q2),
-                               k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
+            crt_prep(Lc, Lc);
             if ((rc = Lc.prog_raw(prog + F.off_p, F.mm_crt, k->mp2, rp, 2))) return rc;
-            hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S, L, Lc.B);
-            mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S,
-                        k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt, out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
+            crt_out(Lc, Lc, cnt, out + off * cw);
         } else if (F.pub_rows) {
             const void *rows[3] = {F.d_tab_pub, dig_p, out + off * cw};
             if ((rc = Lc.prog_raw(prog + F.off_pub, F.mm_pub, k->mn2, rows, 3))) return rc;
@@ -3096,13 +3080,10 @@ static int encrypt_xb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, con
         const void *rq[2] = {X.d_tab[1], dig[1]};
         if ((rc = Lc.prog_raw(X.d_prog + X.off[1], X.mm, X.padic ? k->mqA : k->mq2, rq, 2))) return rc;
         if (X.padic && (rc = Lc.prog(k->prP_encB_q, k->mq2))) return rc;
-        hipLaunchKernelGGL(k_crt_prep_q, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTQ), k->cst(k->c_q2),
-                           k->cst(k->c_2p2), Lc.slot(SL_T0), S, L, Lc.B);
+        crt_prep(Lc, Lc);
         if ((rc = Lc.prog_raw(X.d_prog + X.off[0], X.mm, X.padic ? k->mpA : k->mp2, rp, 2))) return rc;
         if (X.padic && (rc = Lc.prog(k->prP_encB_p, k->mp2))) return rc;
-        hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T2), k->cst(k->c_p2), S, L, Lc.B);
-        mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S,
-                    k->cst(k->c_q2), S, Lc.slot(SL_T2), S, L, cnt, out + off * cw, cw, (uint64_t *)nullptr, Lc.B);
+        crt_out(Lc, Lc, cnt, out + off * cw);
         if (pipe && (rc = pipe->after(off, cnt))) return rc;
     }
     return end_call(c, Lc);
@@ -3134,78 +3115,48 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
     if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
     if (!k->priv) return FTHE_ERR_NOPRIV;
     // Batches that leave most of the chip idle (a GHPair from decrypt_gh, one tree node's sums) run the
-    // c^(q-1) mod q^2 exponentiation on the side stream, in a second slot region, beside c^(p-1) mod p^2:
-    // one exponentiation of latency instead of two.  Large batches fill the chip with one half at a time.
-    // Smaller batches still (<= 16,384 ciphertexts) take both exponentiations on the four-lane s80 kernel,
-    // each Montgomery product spread over a quad of lanes (~3x less latency per exponentiation), and
-    // hand c^(P-1) mod P^2 back to the s74 layout for the unchanged L-function / CRT tail.
-    const int vi = variant_index(k->spq.S);
-    const bool quad = k->slat.S && count > 0 && count <= dec_quad_max() && count <= chunk_lanes();
-    const bool small_split = !quad && !short_pt && vi >= 0 && count * (size_t)kVariants[vi].lanes <= dec_split_lanes();
-    bool split = small_split || (!quad && !short_pt && vi >= 0 && split_all());
-    const int nsl = nslots_for(k);
-    Launch Lc;
-    int rc = begin_call(c, k, count, Lc, split ? 2 * nsl : nsl, k->spq);
-    if (rc == FTHE_ERR_NOMEM && split && !small_split) {     // one region when two do not fit (as encrypt_impl)
-        split = false;
-        rc = begin_call(c, k, count, Lc, nsl, k->spq);
-    }
+    // c^(q-1) mod q^2 exponentiation beside c^(p-1) mod p^2, or both on the four-lane kernel (plan_call);
+    // either way c^(P-1) mod P^2 ends in the s74 slots of the unchanged L-function / CRT tail.
+    CallNeed need;
+    need.dec = true; need.short_pt = short_pt;
+    CallPlan pl;
+    int rc = plan_call(c, k, count, need, pl);
     if (rc) return rc;
+    const bool quad = pl.quad, split = pl.split;
+    Launch &Lc = pl.main, &Lq = pl.q, &Lp4 = pl.p4, &Lq4 = pl.q4;
     const int S = Lc.S, L = Lc.L, nw = k->n_words, cw = 2 * nw;
-    Launch Lp4 = Lc, Lq4 = Lc;             // quad: s80 regions for the p and q halves (slots1)
-    const int wl = (kLatShape.S * kLatShape.B + 31) / 32;   // u32 words of an s80 row
-    uint32_t *rowp = nullptr, *rowq = nullptr;
     if (quad) {
-        if (count > (size_t)L) return FTHE_ERR_ARG;        // one chunk by construction
-        const size_t reg = (size_t)nsl * kLatShape.S * L * 4;
-        if ((rc = c->slots1.ensure(2 * reg))) return rc;
-        if ((rc = c->scratch.ensure((size_t)2 * L * wl * 4))) return rc;
-        rowp = (uint32_t *)c->scratch.p; rowq = rowp + (size_t)L * wl;
-        Lp4.S = kLatShape.S; Lp4.B = kLatShape.B; Lp4.base = c->slots1.p; Lp4.spread = !short_pt;
-        Lq4 = Lp4; Lq4.base = (uint8_t *)c->slots1.p + reg; Lq4.st = c->side;
-        Lp4.fill(SL_C0, k->cl_R2p); Lp4.fill(SL_C1, k->cl_R3p); Lp4.fill(SL_T5, k->cl_one);
-        if (!short_pt) { Lq4.fill(SL_C2, k->cl_R2q); Lq4.fill(SL_C3, k->cl_R3q); Lq4.fill(SL_T5, k->cl_one); }
+        fill_dec_consts(Lp4, kHalfP, true);
+        if (!short_pt) fill_dec_consts(Lq4, kHalfQ, true);
     }
-    Launch Lq = Lc;                        // q half: region 2 of the slots, side stream
     if (split) {
-        Lq.base = (uint8_t *)Lc.base + (size_t)nsl * S * L * 4;
-        Lq.st = c->side;
-        Lc.spread = Lq.spread = true;
-        HIPOK(hipEventRecord(c->ev_fork, c->stream));
-        HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-        Lq.fill(SL_C2, k->c_R2q); Lq.fill(SL_C3, k->c_R3q); Lq.fill(SL_T5, k->c_one);
+        if ((rc = c->side_waits_main())) return rc;
+        fill_dec_consts(Lq, kHalfQ);
     }
-    Launch Lpa, Lpaq;                      // the P-adic kernel's own slots (Paillier-1024; else Lc's)
-    if (!quad && (rc = padic_region(c, k, Lc, Lpa, split ? &Lpaq : nullptr))) return rc;
-    Lc.fill(SL_C0, k->c_R2p); Lc.fill(SL_C1, k->c_R3p);
-    Lc.fill(SL_C2, k->c_R2q); Lc.fill(SL_C3, k->c_R3q);
-    Lc.fill(SL_T5, k->c_one);
+    fill_dec_consts(Lc, kBothHalves);
     for (size_t off = 0; off < count; off += L) {
         size_t cnt = std::min((size_t)L, count - off);
         Lc.live = cnt; Lq.live = cnt;
         if (pipe && (rc = pipe->before(off, L, count))) return rc;
         const uint32_t *src = ct + off * cw;
         if (quad) {
-            const int S4 = kLatShape.S, B4 = kLatShape.B;
+            const int S4 = Lp4.S, B4 = Lp4.B;
             Lp4.live = cnt; Lq4.live = cnt;
             pack_rows(c->stream, src, cw, cnt, 0, Lp4.slot(SL_IN0), S4, L, B4);
             pack_rows(c->stream, src, cw, cnt, B4 * S4, Lp4.slot(SL_IN1), S4, L, B4);
             if (!short_pt) {
                 pack_rows(c->stream, src, cw, cnt, 0, Lq4.slot(SL_IN0), S4, L, B4);
                 pack_rows(c->stream, src, cw, cnt, B4 * S4, Lq4.slot(SL_IN1), S4, L, B4);
-                HIPOK(hipEventRecord(c->ev_fork, c->stream));
-                HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+                if ((rc = c->side_waits_main())) return rc;
                 if ((rc = Lq4.prog(k->pr_dec_ql, k->mq2l))) return rc;
-                HIPOK(hipEventRecord(c->ev_join, c->side));
+                if ((rc = c->side_done())) return rc;
             }
             if ((rc = Lp4.prog(k->pr_dec_pl, k->mp2l))) return rc;
             // canonical c^(P-1) mod P^2 rows -> the s74 slots the tail reads
-            unpack_rows(c->stream, Lp4.slot(SL_OUTP), k->cst(k->cl_p2), S4, L, cnt, rowp, wl, B4);
-            pack_rows(c->stream, rowp, wl, cnt, 0, Lc.slot(SL_OUTP), S, L, Lc.B);
+            quad_hand_back(pl, Lp4, SL_OUTP, k->cl_p2, cnt, pl.rowp);
             if (!short_pt) {
-                HIPOK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                unpack_rows(c->stream, Lq4.slot(SL_OUTQ), k->cst(k->cl_q2), S4, L, cnt, rowq, wl, B4);
-                pack_rows(c->stream, rowq, wl, cnt, 0, Lc.slot(SL_OUTQ), S, L, Lc.B);
+                if ((rc = c->main_waits_side())) return rc;
+                quad_hand_back(pl, Lq4, SL_OUTQ, k->cl_q2, cnt, pl.rowq);
             }
             Lc.mm += Lp4.mm + Lq4.mm; Lp4.mm = Lq4.mm = 0;
         } else {
@@ -3214,12 +3165,11 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
             if (split) {
                 pack_rows(c->stream, src, cw, cnt, 0, Lq.slot(SL_IN0), S, L, Lc.B);
                 pack_rows(c->stream, src, cw, cnt, Lc.B * S, Lq.slot(SL_IN1), S, L, Lc.B);
-                HIPOK(hipEventRecord(c->ev_fork, c->stream));
-                HIPOK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-                if ((rc = dec_pow(Lq, k, 1, &Lpaq))) return rc;
-                HIPOK(hipEventRecord(c->ev_join, c->side));
+                if ((rc = c->side_waits_main())) return rc;
+                if ((rc = dec_pow(Lq, k, 1, &pl.paq))) return rc;
+                if ((rc = c->side_done())) return rc;
             }
-            if ((rc = dec_pow(Lc, k, 0, &Lpa))) return rc;
+            if ((rc = dec_pow(Lc, k, 0, &pl.pa))) return rc;
         }
         if (short_pt) {
             // plaintext < p: m = m_p = L_p(c^(p-1) mod p^2) h_p mod p, the q half and the CRT skipped
@@ -3237,8 +3187,8 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
             continue;
         }
         if (split) {
-            HIPOK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-        } else if (!quad && (rc = dec_pow(Lc, k, 1, &Lpa))) {
+            if ((rc = c->main_waits_side())) return rc;
+        } else if (!quad && (rc = dec_pow(Lc, k, 1, &pl.pa))) {
             return rc;
         }
         hipLaunchKernelGGL(k_dec_lfunc, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTP), k->cst(k->c_p2), S,

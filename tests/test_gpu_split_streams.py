@@ -84,7 +84,7 @@ n = int(sys.argv[2])
 m = np.random.default_rng(5).integers(0, 2**64, n, dtype=np.uint64)
 c = pl.encrypt_u64(m, seed=91)                       # host rows (the staged path)
 ok = bool(np.array_equal(pl.decrypt_u64(c), m))
-md = torch.from_numpy(m.view(np.int64)).cuda()       # device-resident (the bench's path: chunks pipelined)
+md = torch.from_numpy(m.view(np.int64)).cuda()       # device-resident (the bench's path)
 cd = torch.empty((n, 2 * pl.n_words), dtype=torch.int32, device="cuda")
 pl.encrypt_u64_dev(md, cd, seed=91)
 pl.dev.sync()
@@ -99,10 +99,9 @@ print(hashlib.sha256(c.tobytes()).hexdigest(), hashlib.sha256(cdh.tobytes()).hex
 
 def test_split_all_large_calls_bit_identical(tmp_path):
     """Large CRT encrypts and decrypts run each chunk's p and q halves side by side on two streams (fthe.hip
-    split_all, the default), and under FTHE_ENC_PIPE=1 device-resident encrypts pipeline the chunks over two
-    slot-region pairs (enc_pipe, opt-in); FTHE_SPLIT_ALL=0 runs the halves in turn on one stream.
+    split_all, the default); FTHE_SPLIT_ALL=0 runs the halves in turn on one stream.
     Three chunks of 786,432 lanes and a partial fourth, host rows and device rows: the seeded ciphertexts are
-    byte-identical all three ways (and host = device) and decrypt to their plaintexts."""
+    byte-identical both ways (and host = device) and decrypt to their plaintexts."""
     import os
     import subprocess
     import sys
@@ -110,15 +109,15 @@ def test_split_all_large_calls_bit_identical(tmp_path):
     probe = tmp_path / "probe.py"
     probe.write_text(_SPLIT_ALL_PROBE)
     outs = []
-    for split, piped in (("0", "0"), ("1", "0"), ("1", "1")):
+    for split in ("0", "1"):
         r = subprocess.run([sys.executable, str(probe), root, str(3 * 786432 + 5000)], capture_output=True, text=True,
-                           timeout=600, env=dict(os.environ, FTHE_SPLIT_ALL=split, FTHE_ENC_PIPE=piped))
+                           timeout=600, env=dict(os.environ, FTHE_SPLIT_ALL=split))
         assert r.returncode == 0, r.stderr[-3000:]
         outs.append(r.stdout.split())
     for o in outs:
         assert o[2] == "True"
         assert o[0] == o[1]                               # host rows = device rows
-    assert outs[0][0] == outs[1][0] == outs[2][0]
+    assert outs[0][0] == outs[1][0]
 
 
 def test_mem_limit_one_region_fallback():
