@@ -23,8 +23,9 @@ multiply-adds of fthe_padic_k37, and both of their products have a constant oper
   * the limbs that only feed the matrix cores (the upper product halves, q3) are produced with their operand
     bytes already XORed with 0x80 (v_bitop3_b32), so packing them costs no XOR.
 
-Product 1 forms columns 112..271 of q1 mu and yields q3 = Barrett's quotient estimate or one less (q3 is
-clamped to 0 when q1 = 0); product 2 forms columns 0..129 of q3 P (as matrix columns 1..130, the constant
+Product 1 forms columns 128..271 of q1 mu and yields q3 = Barrett's quotient estimate or one less (q3 = -1,
+from a numerator that the truncation bias took below 0, is clamped to 0 where q3 is used as a number; the
+second reduction of a squaring / product folds its q3 straight into product 2's operand dwords); product 2 forms columns 0..129 of q3 P (as matrix columns 1..130, the constant
 digit leading) and r = (T - q3 P) mod b^K exactly.
 The digits stay within [0, 5P) as in fthe_padic_k37 (the bounds are asserted by the model).
 
@@ -84,7 +85,15 @@ KARA = "nokara" not in AB
 assert not (KARA and LDSX)
 assert not (LDSX and (PP or SPILL))
 LDS_BYTES = TILE_BYTES + (4 * SPILL_BYTES if SPILL else 0) + (4 * LDSX_BYTES if LDSX else 0)
-S1_LO = 112                     # product-1 columns S1_LO .. S1_LO + 159
+# product 1's window starts at column 128, not 112: the numerator stays within (Pi - 2^1047, Pi) of Pi = q1 mu
+# (tools/padic_mfma_model.py), which is all Barrett asks, and the 16 columns no longer formed are M-tile 4's rows
+# 16..31 (columns 272..287: zero), which its fold skips; s1lo112 keeps the old window (needs the image of
+# padic_tiles::build(P, 112): A/B in the standalone harness only)
+S1_LO = 112 if "s1lo112" in AB else 128     # product-1 columns S1_LO .. S1_LO + 159
+S1_TOP = 272                    # q1 mu has no column above 271
+# the second reduction's q3 (it only feeds product 2) is folded straight into product 2's operand dwords, radix
+# 2^32 from bit QBIT - 8, in place of 28-bit limbs repacked by orpack; noq3dw keeps the limb fold
+Q3DW = "noq3dw" not in AB and not LDSX
 QBIT = 28 * 38                  # q3 = floor(N / 2^1064)
 TILE_D1 = (-3, -2, -1, 0, 1)    # product-1 Toeplitz tiles (k <= 3) by m - k; then k = 4 for m = 0..4
 TILE_D2 = (0, 1, 2, 3)          # product-2: k = 0 for m = 0..4 (tiles 10..14), then Toeplitz (k >= 1) by m - k
@@ -339,7 +348,12 @@ def gen_padic_mfma(name: str) -> str:
             if xor_masks[w]:
                 e(f'  v_xor_b32_e32 {d}, {hex(xor_masks[w])}, {d}')
 
-    def swap_operands():
+    # the second reduction's product-2 operand block (Q3DW): dwords 0..35 in V[38..73] (its q1 limbs, dead once
+    # packed), 36..39 in the product phase's accumulators v16..v19
+    D2 = [f"v{VV + 38 + i}" for i in range(36)] + [f"v{16 + i}" for i in range(4)]
+    OPND = [D]                                  # the block the MFMAs read their B operands from
+
+    def swap_operands(Dl=D):
         if LDSX:
             # lane r + 32's D[8k + j] <-> lane r's D[8k + 4 + j], as the swaps below; LDS executes one wave's
             # operations in order, and the last one (K-block 4) is never the first tile's first K-block, which
@@ -361,7 +375,7 @@ def gen_padic_mfma(name: str) -> str:
         e('  s_nop 1')
         for k in range(5):
             for j in range(4):
-                e(f'  v_permlane32_swap_b32_e32 {D[8 * k + j]}, {D[8 * k + 4 + j]}')
+                e(f'  v_permlane32_swap_b32_e32 {Dl[8 * k + j]}, {Dl[8 * k + 4 + j]}')
         e('  s_nop 4')
 
     def rd(prod, m, k, n):
@@ -391,14 +405,19 @@ def gen_padic_mfma(name: str) -> str:
             for g, G in ((0, G0x), (1, G1x)):
                 src_c = "0" if n == 0 else f"v[{G}:{G + 15}]"
                 bo = 8 * k + 4 * g
+                b0 = int(OPND[0][bo][1:])
+                assert b0 % 2 == 0 and [int(r[1:]) for r in OPND[0][bo:bo + 4]] == list(range(b0, b0 + 4))
                 if "nomfma" not in AB:
-                    e(f'  v_mfma_i32_32x32x32_i8 v[{G}:{G + 15}], v[{buf}:{buf + 3}], v[{XB + bo}:{XB + bo + 3}], {src_c}')
+                    e(f'  v_mfma_i32_32x32x32_i8 v[{G}:{G + 15}], v[{buf}:{buf + 3}], v[{b0}:{b0 + 3}], {src_c}')
+
+    P1_TOP = [S1_TOP]                            # product 1: the fold reads the columns below this
 
     def consumed(prod, m):
-        """the rows (output columns rho of M-tile m) the fold reads: all of product 1; product 2 drops matrix
-        column 0 (the constant digit's) and the columns above 130"""
+        """the rows (output columns rho of M-tile m) the fold reads: product 1 those below P1_TOP (272: the
+        product's last column, or what the dword fold needs); product 2 drops matrix column 0 (the constant
+        digit's) and the columns above 130"""
         if prod == 1:
-            return set(range(32))
+            return {rho for rho in range(32) if S1_LO + 32 * m + rho < P1_TOP[0]}
         return {rho for rho in range(32) if 1 <= 32 * m + rho <= 130}
 
     def plan(C):
@@ -549,11 +568,15 @@ def gen_padic_mfma(name: str) -> str:
     class Chunks:
         """column sums -> 28-bit limbs.  Chunk t (bits [base + 28 t, +28)) sums its columns (x 2^sh) into its
         own accumulator (two, alternating), independent of the carry; its tail (+ carry, mask, carry out)
-        is deferred into the next chunk's multiply-adds, so the carry chain never stalls the wave."""
+        is deferred into the next chunk's multiply-adds, so the carry chain never stalls the wave.
+        radix / out: chunks of radix bits whose low dword leaves through out(t, register) -> instructions
+        (the dword fold) instead of a masked limb in outs[t]."""
 
-        def __init__(self, base_bits, t0, t_last, outs, neg, inits=None, nocarry_last=False, px=False):
+        def __init__(self, base_bits, t0, t_last, outs, neg, inits=None, nocarry_last=False, px=False,
+                     radix=B, out=None):
             self.base, self.t, self.t0, self.t_last, self.outs, self.neg = base_bits, t0, t0, t_last, outs, neg
             self.inits, self.nocarry_last, self.px = inits, nocarry_last, px
+            self.radix, self.out = radix, out
             self.pending = []
             self.fresh = True
             self.begun = False
@@ -582,7 +605,9 @@ def gen_padic_mfma(name: str) -> str:
             tail = []
             if self.t != self.t0 and not CMERGE:
                 tail.append(f'  v_lshl_add_u64 {a}, {a}, 0, {CCARRY}')
-            if 0 <= self.t < len(self.outs):
+            if self.out is not None:
+                tail += self.out(self.t, f'v{a[2:a.index(":")]}')
+            elif 0 <= self.t < len(self.outs):
                 if self.px:                              # q3 limbs leave pre-flipped (PREXOR)
                     tail.append(f'  v_bitop3_b32 {self.outs[self.t]}, v{a[2:a.index(":")]}, {SMASK}, '
                                 f'{pat(self.t)} bitop3:0x6a')
@@ -590,9 +615,9 @@ def gen_padic_mfma(name: str) -> str:
                     tail.append(f'  v_and_b32_e32 {self.outs[self.t]}, {hex(MASK)}, v{a[2:a.index(":")]}')
             if not (self.nocarry_last and self.t == self.t_last):
                 if CMERGE:                               # the next chunk's first multiply-add reads it
-                    e(f'  v_ashrrev_i64 {CCARRY}, {B}, {a}')
+                    e(f'  v_ashrrev_i64 {CCARRY}, {self.radix}, {a}')
                 else:
-                    tail.append(f'  v_ashrrev_i64 {CCARRY}, {B}, {a}')
+                    tail.append(f'  v_ashrrev_i64 {CCARRY}, {self.radix}, {a}')
             self.pending = tail
             self.t += 1
             self.fresh = True
@@ -600,13 +625,13 @@ def gen_padic_mfma(name: str) -> str:
                 self.start()
 
         def column(self, s, reg):
-            t = (8 * s - self.base) // B
+            t = (8 * s - self.base) // self.radix
             while t > self.t:
                 self.close()
             if not self.begun:
                 self.begun = True
                 self.start()
-            sh = 8 * s - self.base - B * t
+            sh = 8 * s - self.base - self.radix * t
             mul = NEG(sh) if self.neg else POW(sh)
             a = self.acc()
             self.emit(f'  v_mad_i64_i32 {a}, vcc, {reg}, {mul}, {self.addend0() if self.fresh else a}')
@@ -631,8 +656,8 @@ def gen_padic_mfma(name: str) -> str:
             s_, r_, pr_ = cols[i]
             if not pr_ and i + 1 < len(cols) and "nopair" not in AB:
                 s2_, r2_, pr2_ = cols[i + 1]
-                t1, t2 = (8 * s_ - ch.base) // B, (8 * s2_ - ch.base) // B
-                if not pr2_ and s2_ == s_ + 1 and t1 == t2 and 8 * s_ - ch.base - B * t1 <= 16:
+                t1, t2 = (8 * s_ - ch.base) // ch.radix, (8 * s2_ - ch.base) // ch.radix
+                if not pr2_ and s2_ == s_ + 1 and t1 == t2 and 8 * s_ - ch.base - ch.radix * t1 <= 16:
                     e(f'  v_lshl_add_u32 {r_}, {r2_}, 8, {r_}')
                     ch.column(s_, r_)
                     i += 2
@@ -644,11 +669,13 @@ def gen_padic_mfma(name: str) -> str:
     P2_TILES = [(2, m, [k for k in range(5) if m >= k]) for m in range(5)]
     assert P1_TILES[0][2][0] != 4 and P2_TILES[0][2][0] != 4      # LDSX: see swap_operands
 
-    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None):
+    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None, dw=None):
         """product 1: q3 = Barrett's quotient of T (Tl: 2K limbs, Tl[K-1] < 2^29 allowed) -> q3out (K regs,
-        may be Tl[K:]); clamp: q3 = -1 (q1 = 0) -> 0; prefetched: its first A-tile reads are in flight;
+        may be Tl[K:]); clamp: q3 = -1 (numerator < 0: q1 = 0, or a small q1 at P near 2^1030) -> 0; prefetched: its first A-tile reads are in flight;
         dbuf: double-buffered accumulators (T[38..69] free); pre_in: Tl[K..2K-1] arrive pre-flipped
-        (PREXOR, default); q3out leaves pre-flipped under PREXOR"""
+        (PREXOR, default); q3out leaves pre-flipped under PREXOR.
+        dw (no clamp): q3 mod b^K leaves as product 2's operand dwords dw[0..32] instead (byte 0 the constant
+        digit 1, the others b ^ 0x80; tools/padic_mfma_model.py fold_dwords); may overlap Tl[K..]"""
         if pre_in is None:
             pre_in = PREXOR
         if not prefetched:
@@ -659,13 +686,30 @@ def gen_padic_mfma(name: str) -> str:
         for w in range(35, 40):
             e(f'  v_mov_b32_e32 {D[w]}, 0')
         swap_operands()
-        ch = Chunks(QBIT, (8 * S1_LO - QBIT) // B, 39, q3out, neg=False, px=PREXOR)
+        if dw is None:
+            ch = Chunks(QBIT, (8 * S1_LO - QBIT) // B, 39, q3out, neg=False, px=PREXOR)
+        else:
+            assert not clamp
+            base = QBIT - 8                                          # dw[0]'s byte 0 is the constant digit
+
+            def out(w, lo):
+                if w < 0:
+                    return []
+                if w == 0:
+                    return [f'  v_and_b32_e32 {dw[0]}, 0xffffff00, {lo}', f'  v_xor_b32_e32 {dw[0]}, 0x80808001, {dw[0]}']
+                if w == 32:                                          # q3 mod b^K ends at bit 20 of dword 32
+                    return [f'  v_and_b32_e32 {dw[32]}, {hex((1 << (B * K + 8 - 1024)) - 1)}, {lo}',
+                            f'  v_xor_b32_e32 {dw[32]}, 0x80808080, {dw[32]}']
+                return [f'  v_xor_b32_e32 {dw[w]}, 0x80808080, {lo}']
+            ch = Chunks(base, (8 * S1_LO - base) // 32, 32, None, neg=False, nocarry_last=True, radix=32, out=out)
+            P1_TOP[0] = (base + 33 * 32) // 8                        # columns from 264 on lie above dword 32
 
         def consume(m, creg):
             fold_columns(ch, tile_cols(1, m, lambda rho: S1_LO + 32 * m + rho, creg))
         run_tiles(P1_TILES, consume, P2_TILES[0], dbuf, setb=setb)
         ch.finish()
-        if clamp:                                  # final carry = 0, or -1 when q1 = 0 (q3 = -1 -> 0)
+        P1_TOP[0] = S1_TOP
+        if clamp:                                  # final carry = 0, or -1 when the numerator < 0 (q3 = -1 -> 0)
             e(f'  v_not_b32_e32 v{XA + 36}, v{XA + 38}')
             for t, r in enumerate(q3out):
                 if PREXOR:                         # ((r ^ pat) & m) ^ pat
@@ -674,17 +718,21 @@ def gen_padic_mfma(name: str) -> str:
                     e(f'  v_and_b32_e32 {r}, {r}, v{XA + 36}')
         return q3out
 
-    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None):
+    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None, dw=None):
         """product 2: r = (T - q3 P) mod b^K -> rout (may be Tl[:K]); the product-2 tile-0 reads are already
         in flight; nxt_p1: prefetch product 1's first tiles at the end (the next Barrett); after_pack: the
-        caller's last use of the q3 limbs (dbuf may then take their registers)"""
-        orpack(q3, 8, 33, [0x80808000] + [0x80808080] * 32, lead_one=True, pre=range(K) if PREXOR else ())
+        caller's last use of the q3 limbs (dbuf may then take their registers); dw: the operand block whose
+        dwords 0..32 mfma_barrett has written (q3 is None)"""
+        Dl = D if dw is None else dw
+        if dw is None:
+            orpack(q3, 8, 33, [0x80808000] + [0x80808080] * 32, lead_one=True, pre=range(K) if PREXOR else ())
         if after_pack and not dbuf:
             after_pack()
-        e(f'  v_mov_b32_e32 {D[33]}, 0x80')          # q3 byte 131 (zero, offset) at byte 132; pads 0
+        e(f'  v_mov_b32_e32 {Dl[33]}, 0x80')         # q3 byte 131 (zero, offset) at byte 132; pads 0
         for w in range(34, 40):
-            e(f'  v_mov_b32_e32 {D[w]}, 0')
-        swap_operands()
+            e(f'  v_mov_b32_e32 {Dl[w]}, 0')
+        swap_operands(Dl)
+        OPND[0] = Dl
         # matrix column s holds column s - 1 of q3 P (bits 8 s - 8): P'[s - i] is a plain Toeplitz band
         ch = Chunks(8, 0, K - 1, rout, neg=True, inits=Tl[:K], nocarry_last=True)
 
@@ -695,6 +743,7 @@ def gen_padic_mfma(name: str) -> str:
         run_tiles(P2_TILES, consume, P1_TILES[0] if nxt_p1 else None, dbuf,
                   after_issue0=after_pack if dbuf else None)
         ch.finish()
+        OPND[0] = D
 
     # ---- prologue ------------------------------------------------------------
     e('.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
@@ -1076,8 +1125,12 @@ def gen_padic_mfma(name: str) -> str:
                 e(f'  ds_read_b128 v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}], v{V_SPILL} offset:{1024 * j}')
             e(f'  ds_read_b32 {V[K]}, v{V_SPILL} offset:{9 * 1024}')
     mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1)      # u0 -> T[0..K-1]
-    q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf)        # T[K..] is free
-    mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf)
+    if Q3DW:
+        mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2)    # T[K..] is free
+        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2)
+    else:
+        q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf)
+        mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf)
     move(X0, T[:K])
     move(X1, V[:K])
     if PRIO:

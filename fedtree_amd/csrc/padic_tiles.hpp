@@ -3,9 +3,13 @@
 // Restates tools/padic_mfma_model.py MfmaKey.tile_image exactly (tests/test_padic_mfma_model.py compares
 // the two byte for byte).
 //
-//   product 1 (quotient, columns s = 112..271 of q1 mu): A1[s][i] = mu'[s - i] for i < 136 (the lane's
-//     q1 bytes, fed as b - 128), A1[s][136] = g1'[s - 112] (the constant digit 1 of the B operand), 0 above;
-//     g1 = (128 mu sum_{i<136} 256^i - 2^918) >> 896: the -128 offset's correction and the truncation bias;
+//   product 1 (quotient, columns s = 128..271 of q1 mu, matrix rows to 287): A1[s][i] = mu'[s - i] for
+//     i < 136 (the lane's q1 bytes, fed as b - 128), A1[s][136] = g1'[s - 128] (the constant digit 1 of the B
+//     operand), 0 above;
+//     g1 = (128 mu sum_{i<136} 256^i - 2^1046) >> 1024: the -128 offset's correction and the truncation bias
+//     (8 kS1Lo + 22 bits: the columns below kS1Lo and the shift drop less than 2^(8 kS1Lo + 14), so the
+//     numerator the kernel forms lies in (q1 mu - 2^1047, q1 mu); build(P, 112) gives the window of the
+//     kernel's s1lo112 variant, columns 112..271 with a bias of 2^918);
 //     A1[s][137] = mu'[s - 3]: the B digit 16 c there adds c 2^28 mu for the bit 28 of q1's lowest limb;
 //   product 2 (remainder; matrix column s = 1 + the column of q3 P, s = 0..159): A2[s][0] = g2'[s - 1]
 //     (constant digit), A2[s][i] = P'[s - i] for i >= 1 (q3's bytes from digit 1: a plain Toeplitz
@@ -22,7 +26,7 @@
 
 namespace padic_tiles {
 
-constexpr int kTiles = 19, kImageBytes = 20 * 1024, kS1Lo = 112, kNq1 = 136, kConst1 = 136, kNq3 = 132;
+constexpr int kTiles = 19, kImageBytes = 20 * 1024, kS1Lo = 128, kNq1 = 136, kConst1 = 136, kNq3 = 132;
 
 // n balanced base-256 digits of x >= 0; false if they do not hold x
 inline bool balanced(const mpz_t x, int n, std::vector<int> &d) {
@@ -52,10 +56,11 @@ inline void offset_sum(mpz_t out, const mpz_t x, int n) {
     mpz_clear(g);
 }
 
-// the image for P (K = 37 digits: P of 1009..1030 bits); empty on failure
-inline std::vector<uint8_t> build(const mpz_t P) {
+// the image for P (K = 37 digits: P of 1009..1030 bits); empty on failure.  s1lo: product 1's first column
+inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo) {
     std::vector<uint8_t> img;
     if (mpz_sizeinbase(P, 2) < 1009 || mpz_sizeinbase(P, 2) > 1030) return img;
+    if (s1lo != 112 && s1lo != 128) return img;
     mpz_t mu, c, b;
     mpz_inits(mu, c, b, nullptr);
     mpz_set_ui(mu, 1);
@@ -65,9 +70,9 @@ inline std::vector<uint8_t> build(const mpz_t P) {
     bool ok = balanced(mu, 135, mud) && balanced(P, 130, pd);
     offset_sum(c, mu, kNq1);
     mpz_set_ui(b, 1);
-    mpz_mul_2exp(b, b, 918);
+    mpz_mul_2exp(b, b, 8 * s1lo + 22);
     mpz_sub(c, c, b);
-    mpz_fdiv_q_2exp(c, c, 8 * kS1Lo);
+    mpz_fdiv_q_2exp(c, c, 8 * s1lo);
     ok = ok && balanced(c, 160, g1);
     offset_sum(c, P, kNq3);
     mpz_fdiv_r_2exp(c, c, 1040);
@@ -76,7 +81,7 @@ inline std::vector<uint8_t> build(const mpz_t P) {
     if (!ok) return img;
     g2.resize(130);
     auto a1 = [&](int s, int i) -> int {
-        if (i == kConst1) return (s >= kS1Lo && s < kS1Lo + 160) ? g1[s - kS1Lo] : 0;
+        if (i == kConst1) return (s >= s1lo && s < s1lo + 160) ? g1[s - s1lo] : 0;
         if (i == kConst1 + 1) {                 // 16 c, c = bit 28 of q1's lowest limb: mu' shifted 3 bytes
             int j = s - 3;
             return (j >= 0 && j < (int)mud.size()) ? mud[j] : 0;
@@ -100,8 +105,8 @@ inline std::vector<uint8_t> build(const mpz_t P) {
             }
         }
     };
-    for (int d = -3; d <= 1; d++) tile(1, kS1Lo, d >= 0 ? d : 0, d >= 0 ? 0 : -d);
-    for (int m = 0; m < 5; m++) tile(1, kS1Lo, m, 4);
+    for (int d = -3; d <= 1; d++) tile(1, s1lo, d >= 0 ? d : 0, d >= 0 ? 0 : -d);
+    for (int m = 0; m < 5; m++) tile(1, s1lo, m, 4);
     for (int m = 0; m < 5; m++) tile(2, 0, m, 0);
     for (int d = 0; d <= 3; d++) tile(2, 0, d + 1, 1);
     img.resize(kImageBytes, 0);

@@ -9,6 +9,8 @@ for r in 1 2 3; do
   for v in "$@"; do
     # variants named pp* are ping-pong schedules (512-thread workgroups)
     blk=256; [[ $v == pp* ]] && blk=512
+    # variants generated with s1lo112 read the tile image of the window that starts at column 112
+    export M37_S1LO=128; [[ $v == *s1lo112* ]] && export M37_S1LO=112
     M37_BLOCK=$blk timeout -k 10 120 tools/bin/test_padic tools/bin/m37_$v.hsaco $N 0 fthe_padic_m37 > gpurun_out/${T}_one.json
     rc=$?
     # timing-only variants (nomfma, noswap, nonop: wrong results by design) may report bad lanes (rc 1)

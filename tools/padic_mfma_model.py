@@ -17,11 +17,20 @@ column: the B operand carries a constant digit 1 there and the A tiles that colu
 the correction.  So no correction instruction runs on the VALU.
 
 Product 1 (quotient):  q1 = floor(T / b^(K-1)) as bytes i < 136 (its 38 limbs, the lowest one allowed to
-be < 2^29), constant digit at i = 136.  Columns s in [112, 272) are formed; the dropped columns s < 112
-move the sum by less than 2^917.1, so a bias of -2^918 (inside the correction constant) makes the
-computed numerator N satisfy  Pi - 2^920 < N < Pi  for Pi = q1 * mu, i.e. q3 = floor(N / b^(K+1)) is
-Barrett's estimate or one below it.  N < 0 only when q1 = 0 (then Pi = 0, q3 = -1): the kernel clamps
-q3 to 0 there (T < b^36 < P, so 0 is the exact quotient's lower bound and the remainder is T).
+be < 2^29), constant digit at i = 136.  Columns s in [128, 272) are formed (the matrix rows reach 287, all
+zero from 272 on).  With W = 8 S1_LO = 1024:  the column sums are |c_s| <= 138 * 2^14 < 2^21.2, so the
+dropped columns s < 128 hold |L| < 2^21.2 * 256^128 / 255 < 2^(W + 13.3); the constant digit's column
+carries floor((c1 - 2^BIAS) / 2^W), which drops 0 <= delta < 2^W more.  So  Pi - N = 2^BIAS + delta + L
+for Pi = q1 * mu, and with BIAS = W + 22 = 1046:  Pi - 2^1047 < N < Pi, well inside the  Pi - 2^1064 <
+N < Pi  that makes q3 = floor(N / b^(K+1)) Barrett's estimate or one below it.  (Until round 7 the window
+began at column 112 with a bias of 2^918: 21 guard columns, folded for an error of 2^-144 of a quotient
+unit where 2^-17 serves the same statement; MfmaKey(P, s1_lo=112) still builds that form.)
+N < 0 needs Pi < 2^1047, which now also happens for small q1 > 0 when P is near 2^1030 (mu ~ 2^1042);
+then floor(Pi / 2^1064) = 0, so the 0 the kernel clamps q3 = -1 to is Barrett's estimate itself (and
+q1 < 2^1047 / mu + 1 makes T < (q1 + 1) b^36 < P: the remainder is T).  Where the kernel does not clamp
+(the second reduction of a squaring / product), q3 = -1 mod b^K gives r = T + P, the same residue.
+The second reduction's q3 only feeds product 2, so the kernel folds it straight into operand dwords
+(radix 2^32 from bit QBIT - 8, fold_dwords below) -- equal, dword for dword, to packing the limbs.
 Product 2 (remainder):  r = (T - q3 P) mod b^K from columns s < 130 of q3 * P, exact (no truncation):
 constant digit at i = 0, q3's bytes at i = 1..132; the matrix columns are s + 1, so that digit i meets
 P'[s + 1 - i] (a plain Toeplitz matrix, zero above the diagonal band, as the skipped tiles assume).
@@ -43,13 +52,15 @@ import padic_model as pm  # noqa: E402
 B = pm.B
 MASK = pm.MASK
 K = 37
-S1_LO, S1_HI = 112, 272          # product-1 columns (5 M-tiles of 32)
+S1_LO = 128                      # product-1 columns S1_LO .. S1_LO + 159 (5 M-tiles of 32)
+S1_TOP = 272                     # columns >= 272 are zero: the fold reads S1_LO .. S1_TOP - 1
 NQ1 = 136                        # q1 bytes (34 dwords, offset -128)
 CONST1 = 136                     # product-1 constant digit position
 NQ3 = 132                        # q3 bytes (33 dwords after the constant byte), offset -128
 S2_HI = 160                      # product-2 columns 0..159 (only s < 130 are used)
-BIAS_BITS = 918
+BIAS_BITS = 8 * S1_LO + 22       # 1046
 QBIT = B * (K + 1)               # 1064: q3 = floor(N / 2^1064)
+DW_BASE = QBIT - 8               # fold_dwords: chunk w holds bits [DW_BASE + 32 w, + 32)
 TILE_D1 = (-3, -2, -1, 0, 1)     # product-1 Toeplitz tiles (k <= 3), by d = m - k
 TILE_D2 = (0, 1, 2, 3)           # product-2 Toeplitz tiles (k >= 1)
 
@@ -77,21 +88,23 @@ def balanced(x, n):
 
 
 class MfmaKey(pm.PadicKey):
-    def __init__(self, P):
+    def __init__(self, P, s1_lo=S1_LO):
         super().__init__(P, K)
+        assert s1_lo in (112, 128)                          # 112: the window and bias of rounds 2-6
+        self.s1_lo, self.bias_bits = s1_lo, 8 * s1_lo + 22
         mu = pm.value(self.mu)
         self.mu_d = balanced(mu, 135)                       # mu < 2^1063: 134 digits + a carry digit
         self.P_d = balanced(P, 130)                         # P < 2^1031
         c1 = 128 * mu * sum(256 ** i for i in range(NQ1))
-        g1 = (c1 - (1 << BIAS_BITS)) >> (8 * S1_LO)         # a multiple of 256^112: columns >= 112
-        self.g1 = balanced(g1, S1_HI - S1_LO)
+        g1 = (c1 - (1 << self.bias_bits)) >> (8 * s1_lo)    # columns >= s1_lo (the floor drops < 256^s1_lo)
+        self.g1 = balanced(g1, 160)
         c2 = 128 * P * sum(256 ** i for i in range(NQ3))
         self.g2 = balanced(c2 % (1 << 1040), 131)[:130]     # mod 2^1040 (columns < 130; 256^130 = 0 mod b^K)
 
     # A[s][i] of the two products (s: output column, i: B digit index)
     def a1(self, s, i):
         if i == CONST1:
-            return self.g1[s - S1_LO] if S1_LO <= s < S1_HI else 0
+            return self.g1[s - self.s1_lo] if self.s1_lo <= s < self.s1_lo + 160 else 0
         if i == CONST1 + 1:                     # 16 c for the bit 28 of q1's lowest limb (< 2^29)
             j = s - 3
             return self.mu_d[j] if 0 <= j < len(self.mu_d) else 0
@@ -116,9 +129,11 @@ class MfmaKey(pm.PadicKey):
                 for r in range(32):
                     for i in range(32 * k, 32 * k + 32):
                         if m - k > 1:
-                            assert self.a1(S1_LO + 32 * m + r, i) == 0, (m, k)
+                            assert self.a1(self.s1_lo + 32 * m + r, i) == 0, (m, k)
                         if m < k:
                             assert self.a2(32 * m + r, i) == 0, (m, k)
+        for s in range(S1_TOP, self.s1_lo + 160):           # the rows of M-tile 4 that the fold leaves out
+            assert all(self.a1(s, i) == 0 for i in range(160)), s
 
     def tile_image(self):
         """the 19 A tiles as the kernel's LDS image: tile t is 1 KB, lane l's 16 bytes at l * 16
@@ -134,9 +149,9 @@ class MfmaKey(pm.PadicKey):
                     out.append(fn(s_base + 32 * m + r, 32 * k + 16 * h + j) & 255)
         for d in TILE_D1:                       # (m, k) = (d + 3, 3) is one of its instances... any will do
             m, k = (d, 0) if d >= 0 else (0, -d)
-            tile(self.a1, S1_LO, m, k)
+            tile(self.a1, self.s1_lo, m, k)
         for m in range(5):
-            tile(self.a1, S1_LO, m, 4)
+            tile(self.a1, self.s1_lo, m, 4)
         for m in range(5):
             tile(self.a2, 0, m, 0)
         for d in TILE_D2:
@@ -181,27 +196,67 @@ def orpack(limbs_, shift_bits, ndw):
     return [(val >> (32 * w)) & 0xFFFFFFFF for w in range(ndw)]
 
 
-def product1(key, q1):
-    """q1: 38 limbs (q1[0] < 2^29, others < 2^28).  Returns (q3 limbs, clamped).  Bit 28 of q1[0] (c) is
-    fed as the digit 16 c at position 137, whose A column is mu' shifted by 3 bytes."""
+def columns1(key, q1):
+    """the int32 column sums s1_lo .. S1_TOP - 1 of product 1, and Pi = q1 mu"""
     c = q1[0] >> B
     assert c in (0, 1)
     dw = orpack([q1[0] & MASK] + list(q1[1:]), 0, 34) + [1 | (c << 12), 0, 0, 0, 0, 0]
     dig = digits_of(dw, [0x80808080] * 34 + [0] * 6)
     assert dig[CONST1] == 1 and dig[CONST1 + 1] == 16 * c
     col = {}
-    for s in range(S1_LO, S1_HI):
+    for s in range(key.s1_lo, S1_TOP):
         col[s] = s32(sum(key.a1(s, i) * dig[i] for i in range(160) if dig[i]))
+    Pi = pm.value(q1) * pm.value(key.mu)
+    N = sum(v << (8 * s) for s, v in col.items())
+    assert Pi - (1 << (key.bias_bits + 1)) < N < Pi and key.bias_bits + 1 <= QBIT, "Pi - 2^1064 < N < Pi"
+    if N < 0:                                   # the clamped 0 is Barrett's estimate floor(Pi / 2^1064)
+        assert Pi < (1 << QBIT) and pm.value(q1) * (1 << (B * (K - 1))) + (1 << (B * (K - 1))) <= key.P
+    return col, N
+
+
+def fold_limbs(col, s1_lo):
+    """the kernel's limb fold: chunk t holds bits [QBIT + 28 t, + 28) (64-bit sums, arithmetic shifts);
+    returns (the K limbs of q3 mod b^K, the final carry: 0, or -1 for N < 0)"""
     acc = 0
     q3 = []
-    for t in range(-6, 40):
-        for s in range(S1_LO, S1_HI):
+    for t in range((8 * s1_lo - QBIT) // B, 40):
+        for s in col:
             if (8 * s - QBIT) // B == t:
                 acc = pm.s64(acc + (col[s] << (8 * s - QBIT - B * t)))
         if 0 <= t < K:
             q3.append(acc & MASK)
         acc >>= B
     assert acc in (0, -1)
+    return q3, acc
+
+
+def fold_dwords(col, s1_lo):
+    """the second reduction's fold: the 33 operand dwords of product 2 (before the XOR with 0x80) straight from
+    the column sums -- chunk w holds bits [DW_BASE + 32 w, + 32) (64-bit sums, carry = sum >> 32), dword 0's
+    low byte replaced by the constant digit 1, dword 32 cut at q3's bit 28 K.  Columns >= 264 are not read."""
+    acc = 0
+    dw = []
+    for w in range((8 * s1_lo - DW_BASE) // 32, 33):
+        for s in col:
+            if (8 * s - DW_BASE) // 32 == w:
+                acc = pm.s64(acc + (col[s] << (8 * s - DW_BASE - 32 * w)))
+        if w >= 0:
+            dw.append(acc & 0xFFFFFFFF)
+        acc >>= 32
+    dw[0] = (dw[0] & 0xFFFFFF00) | 1
+    dw[32] &= (1 << (B * K + 8 - 32 * 32)) - 1
+    return dw
+
+
+def product1(key, q1):
+    """q1: 38 limbs (q1[0] < 2^29, others < 2^28).  Returns (q3 limbs, clamped).  Bit 28 of q1[0] (c) is
+    fed as the digit 16 c at position 137, whose A column is mu' shifted by 3 bytes."""
+    col, N = columns1(key, q1)
+    q3, acc = fold_limbs(col, key.s1_lo)
+    assert (acc == -1) == (N < 0)
+    want = orpack(q3, 8, 33)                     # the limb fold, packed as product 2's operand
+    want[0] |= 1
+    assert fold_dwords(col, key.s1_lo) == want, "dword fold != orpack(limb fold)"
     clamped = acc == -1
     if clamped:
         assert all(v == MASK for v in q3)

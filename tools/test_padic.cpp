@@ -92,7 +92,8 @@ int main(int argc, char **argv) {
     for (int j = 0; j < K; j++) ctx[j] = (uint32_t)(-(int32_t)pl[j]);
     to_limbs(mu, ctx.data() + K + 3, K + 1);
     {
-        std::vector<uint8_t> img = padic_tiles::build(P);
+        // M37_S1LO=112: the image of code objects generated with the s1lo112 switch (product 1 from column 112)
+        std::vector<uint8_t> img = padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo);
         if (img.empty()) { printf("tile image failed\n"); return 2; }
         memcpy(ctx.data() + 128, img.data(), img.size());
     }

@@ -799,33 +799,44 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
     return bad
 
 
-def m37_selftest(seed=1, ab=None, bits=1024):
+def m37_selftest(seed=1, ab=None, bits=1024, extra=()):
     """wave 0 of fthe_padic_m37 (one workgroup of 256 lanes, 4 waves fill the LDS tile image, wave 0 runs on):
     LOADP x; STOREX t; SQR 1; MUL t; STOREP -> x^3 mod P^2 (< 6 P^2), against Python integers on its 64 lanes
-    (x < P^2: 0, 1, P - 1, P, P^2 - 1 and random).  ab: a generator switch string (FTHE_GEN_M37_AB)."""
+    (x < P^2: 0, 1, P - 1, P, P^2 - 1, the values of extra and random).  ab: a generator switch string
+    (FTHE_GEN_M37_AB)."""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
     sys.path.insert(0, here)
-    if ab is not None:
-        os.environ["FTHE_GEN_M37_AB"] = ab
     import importlib
     import gen_padic_mfma as gm
-    gm = importlib.reload(gm)
+    saved = os.environ.get("FTHE_GEN_M37_AB")
+    if ab is not None:
+        os.environ["FTHE_GEN_M37_AB"] = ab
+    try:
+        gm = importlib.reload(gm)
+        asm = gm.gen_padic_mfma('fthe_padic_m37')
+        s1_lo = gm.S1_LO
+    finally:
+        if saved is None:
+            os.environ.pop("FTHE_GEN_M37_AB", None)
+        else:
+            os.environ["FTHE_GEN_M37_AB"] = saved
+        importlib.reload(gm)
     import padic_mfma_model as mm
     rng = random.Random(seed)
     P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
     P2 = P * P
     K, S, L, B = 37, 74, 256, 28
-    asm = gm.gen_padic_mfma('fthe_padic_m37')
     nv = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', asm).group(1))
     lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
     ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
     for j in range(K):                                           # -P limbs (int32)
         ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
-    img = mm.MfmaKey(P).tile_image()
+    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
     ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
     xs = [rng.randrange(P2) for _ in range(L)]
     xs[:5] = [0, 1, P - 1, P, P2 - 1]
+    xs[5:5 + len(extra)] = [x % P2 for x in extra]
     IN, TAB, OUT = 0, 1, 2
     slots = bytearray(3 * S * L * 4)
     for g_, x in enumerate(xs):
@@ -872,6 +883,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030):
     try:
         gm = importlib.reload(gm)
         asm = gm.gen_padic_mfma('fthe_padic_m37')
+        s1_lo = gm.S1_LO                                          # the s1lo112 switch needs the matching image
     finally:
         if saved is None:
             os.environ.pop("FTHE_GEN_M37_AB", None)
@@ -899,7 +911,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030):
     ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
     for j in range(K):
         ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & MASK)) & M32).to_bytes(4, 'little')
-    img = mm.MfmaKey(P).tile_image()
+    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
     ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
     IN, OUT = 0, 1
     slots = bytearray(2 * S * L * 4)
