@@ -208,7 +208,11 @@ class Paillier:
         key = ctypes.c_void_p()
         _lib.check(self.lib.fthe_key_from_primes(self.dev.ctx, _ptr(pw), _ptr(qw), hw, ctypes.byref(key)),
                    "key_from_primes")
-        return self._adopt(key)
+        self._adopt(key)
+        # fthe_key_export has (n_words + 1) / 2 words per prime and gives 0 for one that needs more (primes of
+        # unequal word counts); the key keeps them in the order given
+        self.p, self.q = int(p), int(q)
+        return self
 
     @classmethod
     def from_public(cls, n, device=None):

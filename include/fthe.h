@@ -114,7 +114,9 @@ void fthe_key_destroy(fthe_key *key);
 int  fthe_key_n_words(const fthe_key *key);
 int  fthe_key_n_bits(const fthe_key *key);
 int  fthe_key_has_private(const fthe_key *key);
-/* Each output (nullable) is n_words words; p and q are n_words/2 words. */
+/* Each output (nullable) is n_words words; p and q are (n_words + 1) / 2 words.  A prime that needs
+ * more (fthe_key_from_primes with primes of unequal word counts, e.g. 1024 and 1025 bits) is
+ * exported as 0: such a caller keeps the primes it passed in. */
 int  fthe_key_export(const fthe_key *key, uint32_t *n, uint32_t *lambda,
                      uint32_t *mu, uint32_t *p, uint32_t *q);
 
