@@ -66,6 +66,9 @@ def build_kernels():
                         lambda K=K: gen_padic.gen_padic(K, 28, f"fthe_padic_k{K}")))
     # the K = 37 P-adic kernel with matrix-core Barrett reductions: pseudo-variant 1137
     kernels.append((1137, "fthe_padic_m37", "padic_m37", lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37")))
+    # its four-tile body (product 2 of the reductions without its fifth M-tile): pseudo-variant 1237
+    kernels.append((1237, "fthe_padic_m37t", "padic_m37t",
+                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37t", top_est=True)))
     # the n-adic four-lane kernel of the public-key encrypt (base-n digits of 76 limbs): pseudo-variant 2076
     kernels.append((2076, "fthe_nadic_q76", "nadic_q76", lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_q76")))
     # its Montgomery form (LSB-first reductions, no quotient estimates): pseudo-variant 2176

@@ -44,22 +44,27 @@ using namespace fthe;
 
 namespace {
 
-constexpr int MAX_VARIANTS = 10;
+constexpr int MAX_VARIANTS = 11;
 // s80: four lanes per element mod p^2 / q^2 of Paillier-2048 (small-batch decrypt latency);
 // 1000 + K: the P-adic exponentiation kernels mod P^2 (gen_padic.py, digits of K limbs, slots of 2K
 // limbs; the "S" here only names the variant): K = 37 runs on the s74 slots of Paillier-2048,
 // K = 19 on slots of its own (38 limbs) for Paillier-1024;
 // 1137: the K = 37 P-adic kernel with matrix-core (MFMA) Barrett reductions (gen_padic_mfma.py), same
 // slots and programs, no fixed-base table ops;
+// 1237: its four-tile body fthe_padic_m37t (gen_padic_mfma.py top_est) for P of at most kPadicTopBits bits; its
+// launches are also counted under 1137 (fthe_prof_read), so 1237 only tells which body ran;
 // 2000 + 76: the n-adic four-lane kernel (gen_nadic.py, base-n digits of 76 limbs) on the s152 slots;
 // 2100 + 76: its Montgomery form (gen_nadic.py mont: LSB-first reductions, no quotient estimates)
 // 2200 + 76: its matrix-core Barrett form (gen_nadicb.py: the products on the VALU, both Barrett reductions by n
 // on i8 MFMA; workgroups of kNbWaves waves, n of 2041..2048 bits)
 constexpr int kPadicS = 1037, kPadicK = 37, kPadicSmallK = 19, kNadicS = 2076, kPadicMfmaS = 1137,
-              kNadicMontS = 2176, kNadicBarS = 2276;
+              kNadicMontS = 2176, kNadicBarS = 2276, kPadicMfmaTS = 1237;
+// fthe_padic_m37t: the widest P (TOPEST_MAX_BITS of gen_padic_mfma.py), Pt = P >> kPadicPtShift at ctx word kPadicPtWord
+constexpr int kPadicTopBits = 1027, kPadicPtShift = 1000, kPadicPtWord = 100;
 const Shape kVariants[MAX_VARIANTS] = {{37, 28, 1}, {74, 28, 1}, {152, 27, 4}, {80, 27, 4},
                                        {1000 + kPadicK, 28, 1}, {1000 + kPadicSmallK, 28, 1}, {kNadicS, 27, 4},
-                                       {kPadicMfmaS, 28, 1}, {kNadicMontS, 27, 4}, {kNadicBarS, 27, 4}};
+                                       {kPadicMfmaS, 28, 1}, {kNadicMontS, 27, 4}, {kNadicBarS, 27, 4},
+                                       {kPadicMfmaTS, 28, 1}};
 constexpr Shape kLatShape{80, 27, 4};
 constexpr int kAddbBlob = 3152;           // fthe_addb_q152's code object in gen/montprog_blobs.h
 
@@ -572,6 +577,7 @@ extern "C" int fthe_ctx_create(int device, fthe_ctx **out) {
         if (kVariants[i].S > 2200) snprintf(name, sizeof name, "fthe_nadic_b%d", kVariants[i].S - 2200);
         else if (kVariants[i].S > 2100) snprintf(name, sizeof name, "fthe_nadic_m%d", kVariants[i].S - 2100);
         else if (kVariants[i].S > 2000) snprintf(name, sizeof name, "fthe_nadic_q%d", kVariants[i].S - 2000);
+        else if (kVariants[i].S > 1200) snprintf(name, sizeof name, "fthe_padic_m%dt", kVariants[i].S - 1200);
         else if (kVariants[i].S > 1100) snprintf(name, sizeof name, "fthe_padic_m%d", kVariants[i].S - 1100);
         else if (kVariants[i].S > 1000) snprintf(name, sizeof name, "fthe_padic_k%d", kVariants[i].S - 1000);
         else snprintf(name, sizeof name, "fthe_montprog_s%d", kVariants[i].S);
@@ -703,6 +709,10 @@ extern "C" int fthe_prof_read(fthe_ctx *c, double *kernel_ms, double *launches, 
         if (c->prof_mm[i] >= 64) {                            // exponentiation launches
             etot += ms; en += 1;
             c->var_ms[c->prof_vi[i]] += ms; c->var_n[c->prof_vi[i]] += 1;
+            if (kVariants[c->prof_vi[i]].S == kPadicMfmaTS) {     // the same kernel family: read as 1137 too
+                const int vm = variant_index(kPadicMfmaS);
+                c->var_ms[vm] += ms; c->var_n[vm] += 1;
+            }
             eiv.emplace_back(t0, (double)t0 + ms);
         }
     }
@@ -755,7 +765,9 @@ static int padic_digits(const mpz_t P, Shape sh) {
 }
 // K = 37 also carries the LDS tile image of fthe_padic_m37 (padic_tiles.hpp) at byte 512 of the context,
 // and the MFMA-Barrett kernel then runs the key's exponentiation programs; FTHE_NO_PADIC_MFMA=1 keeps
-// them on fthe_padic_k37 (bit-identical results).
+// them on fthe_padic_k37 (bit-identical results).  P of at most kPadicTopBits bits takes the four-tile body
+// fthe_padic_m37t (Pt at ctx word kPadicPtWord, above mu's limbs); FTHE_NO_M37T=1 keeps fthe_padic_m37
+// (bit-identical results).
 static int upload_padic(DevMod &d, const mpz_t P, int K) {
     Mpz P2; mpz_mul(P2, P, P);
     d.m.init(P2, Shape{2 * K, 28, 1});
@@ -768,10 +780,16 @@ static int upload_padic(DevMod &d, const mpz_t P, int K) {
     Mpz mu; mpz_set_ui(mu, 1); mpz_mul_2exp(mu, mu, 56 * K); mpz_fdiv_q(mu, mu, P);
     std::vector<uint32_t> ml = to_limbs(mu, K + 1, 28);
     std::copy(ml.begin(), ml.end(), w.begin() + K + pad);
+    if (!tiles.empty()) {
+        static_assert(kPadicPtWord >= 2 * kPadicK + 1 + 3 && kPadicPtWord < 128, "Pt between mu and the tile image");
+        Mpz pt; mpz_fdiv_q_2exp(pt, P, kPadicPtShift);
+        w[kPadicPtWord] = (uint32_t)mpz_get_ui(pt);
+    }
     if (hipMalloc(&d.d_ctx, w.size() * 4) != hipSuccess) return FTHE_ERR_NOMEM;
     HIPOK(hipMemcpy(d.d_ctx, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     d.kernel_S = 1000 + K;
-    d.kernel_S_mfma = tiles.empty() ? 0 : kPadicMfmaS;
+    const bool top_est = !tiles.empty() && mpz_sizeinbase(P, 2) <= (size_t)kPadicTopBits && !getenv("FTHE_NO_M37T");
+    d.kernel_S_mfma = tiles.empty() ? 0 : top_est ? kPadicMfmaTS : kPadicMfmaS;
     return FTHE_OK;
 }
 // Algorithmic 32-bit MACs of a P-adic program (SURVEY 8(d) units, the executed algorithm): s = words

@@ -32,6 +32,10 @@ The digits stay within [0, 5P) as in fthe_padic_k37 (the bounds are asserted by 
 Ops: those of gen_padic.py except the fixed-base table ops (LOADXGD / MULGD), which the host keeps on
 fthe_padic_k37:  0 END, 1 LOADX, 2 STOREX, 3 SQR, 4 MUL, 22 LOADP, 23 STOREP.
 ctx: [-P limbs (K, int32) ...] as for fthe_padic_k37, and the LDS tile image at byte 512 (20 KB).
+
+Two bodies: fthe_padic_m37 (the default output, above) and fthe_padic_m37t (top_est=True, for P of at most
+TOPEST_MAX_BITS bits), whose product 2 in the reductions of SQR / MUL runs four M-tiles and takes r's bits above
+1015 from product 1's fraction (see gen_padic_mfma's docstring); its ctx also holds Pt = P >> 1000 at byte PT_OFF.
 """
 import os
 import sys
@@ -105,7 +109,24 @@ def tile_index(prod, m, k):
     return 10 + m if k == 0 else 15 + TILE_D2.index(m - k)
 
 
-def gen_padic_mfma(name: str) -> str:
+# the four-tile body (gen_padic_mfma(name, top_est=True): fthe_padic_m37t): product 2 of the reductions of SQR / MUL
+# forms bits 0..1015 of r only (M-tiles 0..3, K-blocks 0..3) and takes the rest of limb 36 from product 1's fraction
+TOPEST_MAX_BITS = 1027          # the widest P the four-tile body admits (tools/padic_mfma_model.py asserts why)
+PT_OFF = 400                    # ctx byte offset of Pt = P >> PT_SHIFT (bytes 312..511 are otherwise unused)
+PT_SHIFT = 1000
+TOPEST_C = 128 << 8             # the window constant c = 128 units of 2^1008, in units of 2^1000
+
+
+def gen_padic_mfma(name: str, top_est: bool = False) -> str:
+    """top_est: the four-tile body.  In the reductions of SQR and MUL product 2 runs M-tiles 0..3 only (K-blocks
+    0..3 of the operand: 20 MFMAs instead of 30), which give r mod 2^1016 exactly, and bits 1016.. of r follow from
+    f = frac(N / 2^1064), the guard bits product 1's fold passes through anyway: r = P (f + e) with
+    0 <= e P < 2^1015, so with E = floor(f32 Pt / 2^32) (units of 2^1000) and b = bits 1008..1015 of r,
+    limb 36 = b | ((E + c - 256 b) >> 16) << 8  (derivation, bounds and slack: tools/padic_mfma_model.py).
+    Contract: P of at most TOPEST_MAX_BITS bits; the digits SQR and MUL read (from LOADP, LOADX of a STOREX, or
+    the raw digits of a slot) are below 3P -- 2P plus room for P just above 2^1008, where a digit may leave a
+    little above 2P -- and the digits they leave are below P + 2^1015 (< 3P, < P + 2^1016).  LOADP's input is a
+    plain residue below 3 P^2 (x1 = its quotient); its own reduction keeps the five-tile product 2."""
     K, B = 37, 28
     MASK = (1 << B) - 1
     # ---- VGPR plan ---------------------------------------------------------
@@ -152,6 +173,9 @@ def gen_padic_mfma(name: str) -> str:
         NSGPR = SHI + 2
     if KARA:                                     # s76..s78: 2, 3, 4 x mask
         NSGPR = 79
+    SPT = NSGPR                                  # top_est: Pt = P >> 1000
+    if top_est:
+        NSGPR += 1
     POW = lambda sh: f"s{SPOW + sh // 4}"
     NEG = lambda sh: f"s{SNEG + sh // 4}"
     NP = lambda j: f"s{SNP + j}"
@@ -353,8 +377,9 @@ def gen_padic_mfma(name: str) -> str:
     D2 = [f"v{VV + 38 + i}" for i in range(36)] + [f"v{16 + i}" for i in range(4)]
     OPND = [D]                                  # the block the MFMAs read their B operands from
 
-    def swap_operands(Dl=D):
+    def swap_operands(Dl=D, nk=5):
         if LDSX:
+            assert nk == 5
             # lane r + 32's D[8k + j] <-> lane r's D[8k + 4 + j], as the swaps below; LDS executes one wave's
             # operations in order, and the last one (K-block 4) is never the first tile's first K-block, which
             # issue_tile's lgkmcnt counts then leave the only exchange operation possibly still in flight
@@ -373,7 +398,7 @@ def gen_padic_mfma(name: str) -> str:
             e('  s_mov_b64 exec, -1')
             return
         e('  s_nop 1')
-        for k in range(5):
+        for k in range(nk):
             for j in range(4):
                 e(f'  v_permlane32_swap_b32_e32 {Dl[8 * k + j]}, {Dl[8 * k + 4 + j]}')
         e('  s_nop 4')
@@ -514,9 +539,10 @@ def gen_padic_mfma(name: str) -> str:
         """all M-tiles of a product: consume(m, col_reg_of_the_tile) after each; dbuf: two accumulator sets,
         tile m+1's MFMAs issued before tile m's results are folded, so the matrix core works while the
         lane does (needs T[38..69] free); tile 0's first A tiles are prefetched by the caller"""
+        nt = len(tiles)
         if not dbuf:
-            for m in range(5):
-                mtile_mfmas(*tiles[m], nxt=tiles[m + 1] if m < 4 else nxt)
+            for m in range(nt):
+                mtile_mfmas(*tiles[m], nxt=tiles[m + 1] if m < nt - 1 else nxt)
                 consume(m, col_reg)
             return
         sets = ((G0, G1), setb or (GB0, GB1))
@@ -527,8 +553,8 @@ def gen_padic_mfma(name: str) -> str:
             for ins in work:
                 e(ins)
             separated = len(work) >= MARGIN
-        for m in range(5):
-            if m < 4:
+        for m in range(nt):
+            if m < nt - 1:
                 nxt_issue = capture(lambda: issue_tile(*tiles[m + 1], *sets[(m + 1) % 2], prefetched=False))
             else:
                 nxt_issue = capture(lambda: prefetch(*nxt)) if nxt is not None else []
@@ -570,10 +596,12 @@ def gen_padic_mfma(name: str) -> str:
         own accumulator (two, alternating), independent of the carry; its tail (+ carry, mask, carry out)
         is deferred into the next chunk's multiply-adds, so the carry chain never stalls the wave.
         radix / out: chunks of radix bits whose low dword leaves through out(t, register) -> instructions
-        (the dword fold) instead of a masked limb in outs[t]."""
+        (the dword fold) instead of a masked limb in outs[t].  tap: {t: register -> instructions} run on chunk
+        t's low dword beside its limb (top_est: the fraction below QBIT)."""
 
         def __init__(self, base_bits, t0, t_last, outs, neg, inits=None, nocarry_last=False, px=False,
-                     radix=B, out=None):
+                     radix=B, out=None, tap=None):
+            self.tap = tap or {}
             self.base, self.t, self.t0, self.t_last, self.outs, self.neg = base_bits, t0, t0, t_last, outs, neg
             self.inits, self.nocarry_last, self.px = inits, nocarry_last, px
             self.radix, self.out = radix, out
@@ -605,6 +633,8 @@ def gen_padic_mfma(name: str) -> str:
             tail = []
             if self.t != self.t0 and not CMERGE:
                 tail.append(f'  v_lshl_add_u64 {a}, {a}, 0, {CCARRY}')
+            if self.t in self.tap:
+                tail += self.tap[self.t](f'v{a[2:a.index(":")]}')
             if self.out is not None:
                 tail += self.out(self.t, f'v{a[2:a.index(":")]}')
             elif 0 <= self.t < len(self.outs):
@@ -669,13 +699,19 @@ def gen_padic_mfma(name: str) -> str:
     P2_TILES = [(2, m, [k for k in range(5) if m >= k]) for m in range(5)]
     assert P1_TILES[0][2][0] != 4 and P2_TILES[0][2][0] != 4      # LDSX: see swap_operands
 
-    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None, dw=None):
+    V_FRAC = XA + 37                            # top_est: f32, the 32 bits of N below QBIT (v57)
+    assert V_FRAC not in range(G0, G0 + 32) and V_FRAC not in range(XA + 32, XA + 37) and \
+        V_FRAC not in (XA + 38, XA + 39) and V_FRAC < XB and V_FRAC >= CARRY + 2 and V_FRAC not in VA
+
+    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None, dw=None, t4=False):
         """product 1: q3 = Barrett's quotient of T (Tl: 2K limbs, Tl[K-1] < 2^29 allowed) -> q3out (K regs,
         may be Tl[K:]); clamp: q3 = -1 (numerator < 0: q1 = 0, or a small q1 at P near 2^1030) -> 0; prefetched: its first A-tile reads are in flight;
         dbuf: double-buffered accumulators (T[38..69] free); pre_in: Tl[K..2K-1] arrive pre-flipped
         (PREXOR, default); q3out leaves pre-flipped under PREXOR.
         dw (no clamp): q3 mod b^K leaves as product 2's operand dwords dw[0..32] instead (byte 0 the constant
-        digit 1, the others b ^ 0x80; tools/padic_mfma_model.py fold_dwords); may overlap Tl[K..]"""
+        digit 1, the others b ^ 0x80; tools/padic_mfma_model.py fold_dwords); may overlap Tl[K..]
+        t4 (top_est): f32 -> V_FRAC for the four-tile product 2, which reads operand dwords 0..31 only: the dword
+        fold ends at dword 31"""
         if pre_in is None:
             pre_in = PREXOR
         if not prefetched:
@@ -687,10 +723,17 @@ def gen_padic_mfma(name: str) -> str:
             e(f'  v_mov_b32_e32 {D[w]}, 0')
         swap_operands()
         if dw is None:
-            ch = Chunks(QBIT, (8 * S1_LO - QBIT) // B, 39, q3out, neg=False, px=PREXOR)
+            # chunk -1 is bits 1036..1063 of N: f32 = its 28 bits over four zeros
+            tap = {-1: lambda lo: [f'  v_lshlrev_b32_e32 v{V_FRAC}, 4, {lo}']} if t4 else None
+            ch = Chunks(QBIT, (8 * S1_LO - QBIT) // B, 39, q3out, neg=False, px=PREXOR, tap=tap)
         else:
             assert not clamp
             base = QBIT - 8                                          # dw[0]'s byte 0 is the constant digit
+
+            ndw = 32 if t4 else 33
+            # chunk -1 is bits 1024..1055 of N, chunk 0's low byte bits 1056..1063: f32 = bits 1032..1063
+            tap = {-1: lambda lo: [f'  v_mov_b32_e32 v{V_FRAC}, {lo}'],
+                   0: lambda lo: [f'  v_alignbit_b32 v{V_FRAC}, {lo}, v{V_FRAC}, 8']} if t4 else None
 
             def out(w, lo):
                 if w < 0:
@@ -701,8 +744,9 @@ def gen_padic_mfma(name: str) -> str:
                     return [f'  v_and_b32_e32 {dw[32]}, {hex((1 << (B * K + 8 - 1024)) - 1)}, {lo}',
                             f'  v_xor_b32_e32 {dw[32]}, 0x80808080, {dw[32]}']
                 return [f'  v_xor_b32_e32 {dw[w]}, 0x80808080, {lo}']
-            ch = Chunks(base, (8 * S1_LO - base) // 32, 32, None, neg=False, nocarry_last=True, radix=32, out=out)
-            P1_TOP[0] = (base + 33 * 32) // 8                        # columns from 264 on lie above dword 32
+            ch = Chunks(base, (8 * S1_LO - base) // 32, ndw - 1, None, neg=False, nocarry_last=True, radix=32,
+                        out=out, tap=tap)
+            P1_TOP[0] = (base + ndw * 32) // 8                       # columns from 264 (260) on lie above the last dword
 
         def consume(m, creg):
             fold_columns(ch, tile_cols(1, m, lambda rho: S1_LO + 32 * m + rho, creg))
@@ -718,20 +762,26 @@ def gen_padic_mfma(name: str) -> str:
                     e(f'  v_and_b32_e32 {r}, {r}, v{XA + 36}')
         return q3out
 
-    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None, dw=None):
+    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None, dw=None, t4=False, clamped=False):
         """product 2: r = (T - q3 P) mod b^K -> rout (may be Tl[:K]); the product-2 tile-0 reads are already
         in flight; nxt_p1: prefetch product 1's first tiles at the end (the next Barrett); after_pack: the
         caller's last use of the q3 limbs (dbuf may then take their registers); dw: the operand block whose
-        dwords 0..32 mfma_barrett has written (q3 is None)"""
+        dwords 0..32 mfma_barrett has written (q3 is None)
+        t4 (top_est): M-tiles 0..3 over operand dwords 0..31 (the constant digit and q3 bytes 0..126) give bits
+        0..1015 of r; limb 36 = b | h << 8 with b = bits 1008..1015 and h from V_FRAC (see gen_padic_mfma's
+        docstring); clamped: mfma_barrett forced a negative quotient to 0 (r = T < 2^1016): h = 0 under its mask"""
         Dl = D if dw is None else dw
+        nk = 4 if t4 else 5
         if dw is None:
-            orpack(q3, 8, 33, [0x80808000] + [0x80808080] * 32, lead_one=True, pre=range(K) if PREXOR else ())
+            orpack(q3, 8, 32 if t4 else 33, [0x80808000] + [0x80808080] * 32, lead_one=True,
+                   pre=range(K) if PREXOR else ())
         if after_pack and not dbuf:
             after_pack()
-        e(f'  v_mov_b32_e32 {Dl[33]}, 0x80')         # q3 byte 131 (zero, offset) at byte 132; pads 0
-        for w in range(34, 40):
-            e(f'  v_mov_b32_e32 {Dl[w]}, 0')
-        swap_operands(Dl)
+        if not t4:
+            e(f'  v_mov_b32_e32 {Dl[33]}, 0x80')         # q3 byte 131 (zero, offset) at byte 132; pads 0
+            for w in range(34, 40):
+                e(f'  v_mov_b32_e32 {Dl[w]}, 0')
+        swap_operands(Dl, nk)
         OPND[0] = Dl
         # matrix column s holds column s - 1 of q3 P (bits 8 s - 8): P'[s - i] is a plain Toeplitz band
         ch = Chunks(8, 0, K - 1, rout, neg=True, inits=Tl[:K], nocarry_last=True)
@@ -740,10 +790,23 @@ def gen_padic_mfma(name: str) -> str:
             fold_columns(ch, tile_cols(2, m, lambda rho: 32 * m + rho, creg))
         # dbuf: the caller's last use of q3 runs while tile 0 (first accumulator set) is in the matrix core;
         # the second set (q3's registers) is first written by tile 1
-        run_tiles(P2_TILES, consume, P1_TILES[0] if nxt_p1 else None, dbuf,
+        run_tiles(P2_TILES[:nk], consume, P1_TILES[0] if nxt_p1 else None, dbuf,
                   after_issue0=after_pack if dbuf else None)
         ch.finish()
         OPND[0] = D
+        if t4:
+            # tiles 0..3 leave chunk 36 = (T[36] + carry - column 127) mod 2^28: its low byte is exact
+            lo, hi = XA + 32, XA + 33                                # the chunk sums are free again
+            vb, vh = f'v{XA + 34}', f'v{XA + 35}'
+            e(f'  v_mad_u64_u32 {pair(lo)}, vcc, v{V_FRAC}, s{SPT}, 0')   # hi = E = floor(f32 Pt / 2^32)
+            e(f'  v_and_b32_e32 {vb}, 0xff, {rout[K - 1]}')
+            e(f'  v_lshlrev_b32_e32 {vh}, 8, {vb}')
+            e(f'  v_sub_u32_e32 {vh}, v{hi}, {vh}')
+            e(f'  v_add_u32_e32 {vh}, {hex(TOPEST_C)}, {vh}')
+            e(f'  v_lshrrev_b32_e32 {vh}, 16, {vh}')
+            if clamped:
+                e(f'  v_and_b32_e32 {vh}, {vh}, v{XA + 36}')
+            e(f'  v_lshl_or_b32 {rout[K - 1]}, {vh}, 8, {vb}')
 
     # ---- prologue ------------------------------------------------------------
     e('.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
@@ -783,6 +846,8 @@ def gen_padic_mfma(name: str) -> str:
             off += 4 * width
             sreg += width
             rem -= width
+    if top_est:
+        e(f'  s_load_dword s{SPT}, s[8:9], {hex(PT_OFF)}')
     for i in range(8):
         e(f'  s_mov_b32 s{SPOW + i}, {hex(1 << (4 * i))}')
     for i in range(7):
@@ -1112,7 +1177,7 @@ def gen_padic_mfma(name: str) -> str:
         for j in range(9):
             e(f'  ds_write_b128 v{V_SPILL}, v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}] offset:{1024 * j}')
         e(f'  ds_write_b32 v{V_SPILL}, {V[K]} offset:{9 * 1024}')
-    q3 = mfma_barrett(T, T[K:], clamp=True, dbuf=spill, setb=(GV0, GV1))    # u1 -> T[K..2K-1]
+    q3 = mfma_barrett(T, T[K:], clamp=True, dbuf=spill, setb=(GV0, GV1), t4=top_est)    # u1 -> T[K..2K-1]
 
     def add_u1():
         for i in range(K):
@@ -1124,13 +1189,13 @@ def gen_padic_mfma(name: str) -> str:
             for j in range(9):
                 e(f'  ds_read_b128 v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}], v{V_SPILL} offset:{1024 * j}')
             e(f'  ds_read_b32 {V[K]}, v{V_SPILL} offset:{9 * 1024}')
-    mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1)      # u0 -> T[0..K-1]
+    mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True)    # u0 -> T[0..K-1]
     if Q3DW:
-        mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2)    # T[K..] is free
-        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2)
+        mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2, t4=top_est)    # T[K..] is free
+        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2, t4=top_est)
     else:
-        q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf)
-        mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf)
+        q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf, t4=top_est)
+        mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf, t4=top_est)
     move(X0, T[:K])
     move(X1, V[:K])
     if PRIO:
@@ -1149,7 +1214,8 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument('--name', default='fthe_padic_m37')
+    ap.add_argument('--top-est', action='store_true', help='the four-tile body (fthe_padic_m37t)')
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:
-        f.write(gen_padic_mfma(a.name))
+        f.write(gen_padic_mfma(a.name, top_est=a.top_est))

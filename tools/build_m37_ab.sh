@@ -1,10 +1,15 @@
 #!/bin/bash
-# timing-only variants of fthe_padic_m37 for the standalone harness (tools/bin/m37_<variant>.hsaco)
+# timing-only variants of fthe_padic_m37 for the standalone harness (tools/bin/m37_<variant>.hsaco); the variant
+# "base" is the default schedule and "t" the four-tile body fthe_padic_m37t:  M37_AB="base t" bash tools/build_m37_ab.sh
 set -e
 L=/opt/rocm/lib/llvm/bin
 for v in ${M37_AB:-noswap nonop nomfma noswap,nonop}; do
   n=${v//,/_}; n=${n/pingpong/pp}
-  FTHE_GEN_M37_AB=$v python3 fedtree_amd/csrc/gen_padic_mfma.py -o /tmp/m37_$n.s
+  if [ "$v" = t ]; then      # the four-tile body, run as fthe_padic_m37t (m37_ab.sh); base: M37_AB="base t" with base = ""
+    python3 fedtree_amd/csrc/gen_padic_mfma.py --name fthe_padic_m37t --top-est -o /tmp/m37_$n.s
+  else
+    FTHE_GEN_M37_AB=${v/#base/} python3 fedtree_amd/csrc/gen_padic_mfma.py -o /tmp/m37_$n.s
+  fi
   $L/clang -x assembler -target amdgcn-amd-amdhsa -mcpu=gfx950 -c /tmp/m37_$n.s -o /tmp/m37_$n.o
   $L/ld.lld -shared /tmp/m37_$n.o -o tools/bin/m37_$n.hsaco
 done

@@ -230,22 +230,158 @@ def fold_limbs(col, s1_lo):
     return q3, acc
 
 
-def fold_dwords(col, s1_lo):
+def fold_dwords(col, s1_lo, ndw=33, frac=None):
     """the second reduction's fold: the 33 operand dwords of product 2 (before the XOR with 0x80) straight from
     the column sums -- chunk w holds bits [DW_BASE + 32 w, + 32) (64-bit sums, carry = sum >> 32), dword 0's
-    low byte replaced by the constant digit 1, dword 32 cut at q3's bit 28 K.  Columns >= 264 are not read."""
+    low byte replaced by the constant digit 1, dword 32 cut at q3's bit 28 K.  Columns >= 264 are not read.
+    ndw = 32 (fthe_padic_m37t): the fold ends at dword 31, columns >= 260 are not read.  frac: a list that
+    receives f32 = bits 1032..1063 of N (chunk -1 and chunk 0's low byte, v_alignbit_b32 by 8)."""
     acc = 0
     dw = []
-    for w in range((8 * s1_lo - DW_BASE) // 32, 33):
+    lowc = {}
+    for w in range((8 * s1_lo - DW_BASE) // 32, ndw):
         for s in col:
             if (8 * s - DW_BASE) // 32 == w:
                 acc = pm.s64(acc + (col[s] << (8 * s - DW_BASE - 32 * w)))
+        lowc[w] = acc & 0xFFFFFFFF
         if w >= 0:
             dw.append(acc & 0xFFFFFFFF)
         acc >>= 32
+    if frac is not None:
+        frac.append(((lowc[0] << 32 | lowc[-1]) >> 8) & 0xFFFFFFFF)
     dw[0] = (dw[0] & 0xFFFFFF00) | 1
-    dw[32] &= (1 << (B * K + 8 - 32 * 32)) - 1
+    if ndw == 33:
+        dw[32] &= (1 << (B * K + 8 - 32 * 32)) - 1
     return dw
+
+
+def frac_limbs(col, s1_lo):
+    """f32 of the first reduction's limb fold: chunk -1 (bits 1036..1063 of N) shifted left by 4"""
+    acc = 0
+    for t in range((8 * s1_lo - QBIT) // B, 0):
+        for s in col:
+            if (8 * s - QBIT) // B == t:
+                acc = pm.s64(acc + (col[s] << (8 * s - QBIT - B * t)))
+        lo = acc & 0xFFFFFFFF
+        acc >>= B
+    return (lo << 4) & 0xFFFFFFFF
+
+
+# ---- fthe_padic_m37t: four-tile product 2, limb 36 from product 1's fraction -------------------------------
+# r = T - q3 P with q3 = floor(N / 2^1064), so r = P (f + e) for f = frac(N / 2^1064) and e = T / P - N / 2^1064:
+#   0 <= e <= 2^1009 / P (q1 drops limbs 0..35 of T; the second reduction's carry u1 in unnormalised limbs below
+#   2^29, so up to 2 b^36) + T / 2^2072 (mu drops < 1) + 2^-17 (Pi - N < 2^1047).
+# So P f <= r < P f + W, W = 2^1009 + T P / 2^2072 + P 2^-17.  The kernel holds f32 = floor(2^32 f) (the dword
+# fold) or its top 28 bits (the limb fold) and Pt = floor(P / 2^1000) and forms E = floor(f32 Pt / 2^32):
+#   0 <= P f / 2^1000 - E < 1 (Pt) + Pt 2^-28 (f32: <= 1/2 for P < 2^1027) + 1 (floor) < 3.
+# Tiles 0..3 give r mod 2^1016 exactly; with b = bits 1008..1015 of r and r = 2^1016 h + 2^1008 b + low, the
+# distance d = r / 2^1000 - E (units of 2^1000) lies in [0, W / 2^1000 + 3), and for 0 <= d <= C = 128 * 256
+#   E + C - 256 b = 65536 h + (low / 2^1000) + (C - d)  in  [65536 h, 65536 h + 255 + C]:  h = (E + C - 256 b) >> 16.
+# (The rule holds for every d in [C - 65535 + 255, C]; the asserted window [0, C] is half of the 256 units.)
+# T is at most TOPEST_T(P) = 2 (3P)^2 + 9P + 1, the cross term of digits below 3P plus u1, so W / 2^1008 <
+# 2 + 18 P^3 / 2^3080 + P / 2^1025: 42.1 units at P < 2^1027 (a third of C), 298 at P < 2^1028 (too wide).
+TOPEST_MAX_BITS = 1027
+PT_SHIFT = 1000
+TOPEST_C = 128 << 8
+TOPEST_DIGIT = 3                 # SQR / MUL digits are below TOPEST_DIGIT * P
+
+
+def topest_t_max(P):
+    return 2 * (TOPEST_DIGIT * P) ** 2 + TOPEST_DIGIT * TOPEST_DIGIT * P + 1
+
+
+def topest_window(P, Tmax=None, low=2 << (B * (K - 1))):
+    """an upper bound of d (units of 2^1000, rounded up) over all T <= Tmax whose limbs 0..35 hold at most low"""
+    Tmax = topest_t_max(P) if Tmax is None else Tmax
+    W = low + -(-Tmax * P >> 2072) + (P >> 17) + 1
+    return -(-W >> PT_SHIFT) + 3
+
+
+def topest_check_key(P):
+    assert P.bit_length() <= TOPEST_MAX_BITS, "fthe_padic_m37t: P wider than the admitted size"
+    assert 2 * topest_window(P) <= 2 * TOPEST_C and topest_window(P) <= TOPEST_C, "window wider than half of 256 units"
+    return topest_window(P)
+
+
+SLACK = {"d_max": 0}             # the largest d seen (tests report it against TOPEST_C)
+
+
+def top_limb(key, r36_low, f32, clamped=False):
+    """limb 36 of r from its exact low byte and f32 (the kernel's seven instructions)"""
+    Pt = key.P >> PT_SHIFT
+    assert Pt < (1 << 32) and 0 <= f32 < (1 << 32)
+    E = (f32 * Pt) >> 32
+    b = r36_low & 0xFF
+    h = ((E + TOPEST_C - (b << 8)) & 0xFFFFFFFF) >> 16
+    if clamped:
+        h = 0
+    return b | (h << 8), E
+
+
+def product2_top(key, dw, T, f32, clamped=False):
+    """the four-tile product 2: operand dwords 0..31 (the constant digit, q3 bytes 0..126), matrix columns
+    1..127 folded as in product2, limb 36 by top_limb"""
+    assert len(dw) == 32
+    dig = digits_of(dw, [0x80808000] + [0x80808080] * 31)
+    assert dig[0] == 1
+    r = []
+    acc = 0
+    for t in range(K):
+        acc = acc + T[t]
+        for s in range(1, 128):
+            if (8 * s - 8) // B == t:
+                c = s32(sum(key.a2(s, i) * dig[i] for i in range(128) if dig[i]))
+                acc = pm.s64(acc - (c << (8 * s - 8 - B * t)))
+        r.append(acc & MASK)
+        acc >>= B
+    r[K - 1], E = top_limb(key, r[K - 1], f32, clamped)
+    return r, E
+
+
+def barrett_top(key, T):
+    """one Barrett as fthe_padic_m37t runs it, in both of its forms: the first reduction's (limb fold, clamp) and
+    the second's (dword fold to dword 31, no clamp).  Asserts: T within the contract, both forms reproduce the
+    five-tile r exactly (the second r + P where the first clamps), d within [0, TOPEST_C] (the candidate is
+    unique with a factor of two to spare), r < P + 2^1015.  Returns (q3, r, clamped) like barrett."""
+    P = key.P
+    topest_check_key(P)
+    Tv = pm.value(T)
+    assert Tv <= topest_t_max(P), "T beyond the contract (digits below 3P)"
+    low = pm.value(T[:K - 1]) + 1
+    assert low <= 2 << (B * (K - 1))
+    q3, r, clamped = barrett(key, T)
+    col, N = columns1(key, T[K - 1:2 * K])
+    rv = pm.value(r)
+    # first form
+    f28 = frac_limbs(col, key.s1_lo)
+    assert f28 == ((N >> (QBIT - 28)) & MASK) << 4
+    dw = orpack(q3, 8, 33)[:32]
+    dw[0] |= 1
+    r1, E1 = product2_top(key, dw, T, f28, clamped)
+    assert r1 == r, "four-tile product 2 (limb fold) != five-tile"
+    # second form
+    fr = []
+    dw2 = fold_dwords({s: c for s, c in col.items() if s < 260}, key.s1_lo, ndw=32, frac=fr)
+    assert fr[0] == (N >> (QBIT - 32)) & 0xFFFFFFFF
+    if clamped:                                  # q3 = -1 mod b^K where the kernel does not clamp: r = T + P
+        assert dw2 == [0xFFFFFF01] + [0xFFFFFFFF] * 31
+        want = pm.limbs(Tv + P, K)
+    else:
+        assert dw2 == dw
+        want = r
+    r2, E2 = product2_top(key, dw2, T, fr[0], False)
+    assert r2 == want, "four-tile product 2 (dword fold) != five-tile"
+    for E, R in ((E1, None if clamped else rv), (E2, pm.value(want))):
+        if R is None:
+            continue
+        d = -(-R >> PT_SHIFT) - E
+        wnd = topest_window(P, Tv, low)
+        assert 0 <= (R >> PT_SHIFT) - E and d <= wnd <= topest_window(P) <= TOPEST_C, (d, wnd)
+        SLACK["d_max"] = max(SLACK["d_max"], d)
+        assert R < P + (1 << 1015)
+    if clamped:
+        assert Tv < (1 << 1016)
+    return q3, r, clamped
 
 
 def product1(key, q1):
@@ -300,6 +436,11 @@ def install():
     pm.barrett = lambda key, T: barrett(key, T)[:2]
 
 
+def install_top():
+    """the same through fthe_padic_m37t's Barrett (loadp too: its inputs below 3 P^2 lie within the contract)"""
+    pm.barrett = lambda key, T: barrett_top(key, T)[:2]
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 12
@@ -342,6 +483,29 @@ def main():
                 assert got % P2 == pow(X, e, P2), t
     print(f"ok: {trials} keys (squaring / product / LOADP through the MFMA Barrett, {nclamp} clamped quotients, "
           f"exponentiations)")
+    # fthe_padic_m37t: digits below 3P, P of at most TOPEST_MAX_BITS bits
+    install_top()
+    for t in range(trials):
+        bits = rng.choice([1009, 1010, 1023, 1024, 1024, 1026, TOPEST_MAX_BITS])
+        P = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
+        key = MfmaKey(P)
+        P2 = P * P
+        top = TOPEST_DIGIT * P - 1
+        for x0v, x1v in ((top, top), (1, 0), (0, 1), (P - 1, P - 1), (2 * P - 1, 2 * P - 1),
+                         (rng.randrange(top), rng.randrange(top))):
+            z0, z1 = pm.sqr(key, pm.limbs(x0v, K), pm.limbs(x1v, K))
+            X = x0v + x1v * P
+            assert (pm.value(z0) + pm.value(z1) * P) % P2 == X * X % P2
+            assert max(pm.value(z0), pm.value(z1)) < P + (1 << 1015)
+            y0, y1 = pm.mul(key, z0, z1, pm.limbs(x0v, K), pm.limbs(x1v, K))
+            assert (pm.value(y0) + pm.value(y1) * P) % P2 == X ** 3 % P2
+            assert max(pm.value(y0), pm.value(y1)) < P + (1 << 1015)
+        if t < 2:
+            X, ex = rng.randrange(P2), rng.getrandbits(48) | 1
+            assert pm.value(pm.padic_pow(key, X, ex)) % P2 == pow(X, ex, P2)
+    install()
+    print(f"ok: {trials} keys through the four-tile product 2 (fthe_padic_m37t): largest distance "
+          f"{SLACK['d_max'] / 256:.2f} of the {TOPEST_C // 256} units asserted (256 between candidates)")
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 // Build: hipcc --offload-arch=gfx950 -O2 -idirafter /opt/conda/include tools/test_padic.cpp -l:libgmp.so.10 -o tools/bin/test_padic
 // Run:   [M37_BLOCK=512] tools/bin/test_padic <hsaco> [lanes] [mode] [kernel]   mode 0: y^P, y < P (encrypt); 1: c^(P-1), c < P^2;
 //        bring-up programs: 2: LOADP; STOREP (c < P^2), 3: LOADP; SQR 1; STOREP, 4: LOADP; SQR 1; MUL IN; STOREP
-//        kernel: fthe_padic_k37 (default) or fthe_padic_m37 (gen_padic_mfma.py: ctx carries the LDS tile image)
+//        kernel: fthe_padic_k37 (default), fthe_padic_m37 (gen_padic_mfma.py: ctx carries the LDS tile image) or
+//        fthe_padic_m37t (its four-tile body: ctx also carries Pt = P >> 1000 at word 100)
 // Checks sampled lanes against GMP's mpz_powm and prints the launch time and products per second.
 #include <hip/hip_runtime.h>
 #include <gmp.h>
@@ -72,6 +73,7 @@ int main(int argc, char **argv) {
     int L = argc > 2 ? atoi(argv[2]) : 65536;
     int mode = argc > 3 ? atoi(argv[3]) : 0;
     std::string kname = argc > 4 ? argv[4] : "fthe_padic_k37";
+    if (getenv("M37_KERNEL") && *getenv("M37_KERNEL")) kname = getenv("M37_KERNEL");   // tools/m37_ab.sh: m37t variants
     const int BLK = getenv("M37_BLOCK") ? atoi(getenv("M37_BLOCK")) : 256;   // 512: ping-pong m37 variants
     if (BLK <= 0 || BLK % 256 || L % BLK) { printf("lanes must be a multiple of the block (%d)\n", BLK); return 2; }
     std::ifstream f(path, std::ios::binary);
@@ -91,6 +93,7 @@ int main(int argc, char **argv) {
     to_limbs(P, pl.data(), K);
     for (int j = 0; j < K; j++) ctx[j] = (uint32_t)(-(int32_t)pl[j]);
     to_limbs(mu, ctx.data() + K + 3, K + 1);
+    mpz_fdiv_q_2exp(t, P, 1000); ctx[100] = (uint32_t)mpz_get_ui(t);     // Pt (gen_padic_mfma.py PT_OFF = 400)
     {
         // M37_S1LO=112: the image of code objects generated with the s1lo112 switch (product 1 from column 112)
         std::vector<uint8_t> img = padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo);

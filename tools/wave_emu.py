@@ -799,11 +799,31 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
     return bad
 
 
-def m37_selftest(seed=1, ab=None, bits=1024, extra=()):
+def _m37_asm(gm, variant):
+    """the kernel text of a variant: 'm37' (fthe_padic_m37) or 'm37t' (fthe_padic_m37t, the four-tile product 2)"""
+    assert variant in ('m37', 'm37t')
+    return gm.gen_padic_mfma('fthe_padic_' + variant, top_est=variant == 'm37t')
+
+
+def _m37_ctx(gm, mm, P, s1_lo, variant):
+    """the key context: -P limbs, Pt = P >> 1000 (m37t), the tile image"""
+    K, B = 37, 28
+    ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
+    for j in range(K):                                           # -P limbs (int32)
+        ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
+    if variant == 'm37t':
+        assert P.bit_length() <= gm.TOPEST_MAX_BITS == mm.TOPEST_MAX_BITS
+        ctx[gm.PT_OFF:gm.PT_OFF + 4] = (P >> gm.PT_SHIFT).to_bytes(4, 'little')
+    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
+    ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
+    return ctx
+
+
+def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None):
     """wave 0 of fthe_padic_m37 (one workgroup of 256 lanes, 4 waves fill the LDS tile image, wave 0 runs on):
     LOADP x; STOREX t; SQR 1; MUL t; STOREP -> x^3 mod P^2 (< 6 P^2), against Python integers on its 64 lanes
     (x < P^2: 0, 1, P - 1, P, P^2 - 1, the values of extra and random).  ab: a generator switch string
-    (FTHE_GEN_M37_AB)."""
+    (FTHE_GEN_M37_AB).  variant: 'm37' or 'm37t'.  P: the modulus (default: random of `bits` bits)."""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
     sys.path.insert(0, here)
@@ -814,7 +834,7 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=()):
         os.environ["FTHE_GEN_M37_AB"] = ab
     try:
         gm = importlib.reload(gm)
-        asm = gm.gen_padic_mfma('fthe_padic_m37')
+        asm = _m37_asm(gm, variant)
         s1_lo = gm.S1_LO
     finally:
         if saved is None:
@@ -824,16 +844,13 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=()):
         importlib.reload(gm)
     import padic_mfma_model as mm
     rng = random.Random(seed)
-    P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
+    if P is None:
+        P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
     P2 = P * P
     K, S, L, B = 37, 74, 256, 28
     nv = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', asm).group(1))
     lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
-    ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
-    for j in range(K):                                           # -P limbs (int32)
-        ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
-    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
-    ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
+    ctx = _m37_ctx(gm, mm, P, s1_lo, variant)
     xs = [rng.randrange(P2) for _ in range(L)]
     xs[:5] = [0, 1, P - 1, P, P2 - 1]
     xs[5:5 + len(extra)] = [x % P2 for x in extra]
@@ -863,15 +880,16 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=()):
             bad += 1
             if bad <= 3:
                 print(f"  lane {g_}: got {got:#x}\n   want {pow(xs[g_], 3, P2):#x}")
-    print(f"m37 ({ab or 'default'}): 64 lanes, {bad} mismatches, {steps} wave-instructions emulated")
+    print(f"{variant} ({ab or 'default'}): 64 lanes, {bad} mismatches, {steps} wave-instructions emulated")
     return bad
 
 
-def m37_digits_selftest(seed=1, ab=None, bits=1030):
+def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs0=()):
     """wave 0 of fthe_padic_m37 on crafted digit pairs (LOADX raw digits; SQR 1; SQR 1; STOREP): the squaring's
-    cross term at the extremes the kernel admits -- every limb < 2^28 and each digit < 5P, incl. digits whose
-    low 36 limbs are all 2^28 - 1 (the largest Karatsuba half sums and column sums), zero halves, one-limb
-    digits and random ones -- against (x0 + x1 P)^4 mod P^2 in Python integers"""
+    cross term at the extremes the kernel admits -- every limb < 2^28 and each digit < 5P (m37t: < 3P, its
+    contract), incl. digits whose low 36 limbs are all 2^28 - 1 (the largest Karatsuba half sums and column
+    sums), zero halves, one-limb digits and random ones -- against (x0 + x1 P)^4 mod P^2 in Python integers.
+    P: the modulus (default: random of `bits` bits); pairs0: digit pairs that take the first lanes."""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
     sys.path.insert(0, here)
@@ -882,7 +900,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030):
         os.environ["FTHE_GEN_M37_AB"] = ab
     try:
         gm = importlib.reload(gm)
-        asm = gm.gen_padic_mfma('fthe_padic_m37')
+        asm = _m37_asm(gm, variant)
         s1_lo = gm.S1_LO                                          # the s1lo112 switch needs the matching image
     finally:
         if saved is None:
@@ -892,27 +910,26 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030):
         importlib.reload(gm)
     import padic_mfma_model as mm
     rng = random.Random(seed)
-    P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
+    if P is None:
+        P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
     P2 = P * P
     K, S, L, B = 37, 74, 256, 28
     MASK = (1 << B) - 1
-    top = 5 * P - 1                                              # the largest digit
+    nd = mm.TOPEST_DIGIT if variant == 'm37t' else 5
+    top = nd * P - 1                                             # the largest digit
     allones = (1 << (B * (K - 1))) - 1                           # limbs 0..35 = 2^28 - 1
     big = allones + (((top - allones) >> (B * (K - 1))) << (B * (K - 1)))
     assert big <= top
     low19 = (1 << (B * 19)) - 1                                  # xL all ones, xH 0
     high18 = big - (big & low19)                                 # xL 0, xH max
     special = [big, 0, 1, low19, high18, top, P - 1, (1 << (B * 19)), MASK, big ^ (MASK << (B * 18))]
-    pairs = [(a, b) for a in special for b in special][:40]
+    pairs = (list(pairs0) + [(a, b) for a in special for b in special])[:max(40, len(pairs0))]
+    assert len(pairs) <= 64 and all(0 <= a <= top and 0 <= b <= top for a, b in pairs)
     while len(pairs) < 64:
-        pairs.append((rng.randrange(5 * P), rng.randrange(5 * P)))
+        pairs.append((rng.randrange(nd * P), rng.randrange(nd * P)))
     nv = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', asm).group(1))
     lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
-    ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
-    for j in range(K):
-        ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & MASK)) & M32).to_bytes(4, 'little')
-    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
-    ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
+    ctx = _m37_ctx(gm, mm, P, s1_lo, variant)
     IN, OUT = 0, 1
     slots = bytearray(2 * S * L * 4)
     for g_, (x0, x1) in enumerate(pairs):
@@ -941,15 +958,15 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030):
             bad += 1
             if bad <= 3:
                 print(f"  lane {g_}: got {got:#x}\n   want {want:#x}")
-    print(f"m37 digits ({ab or 'default'}): 64 lanes, {bad} mismatches, {steps} wave-instructions emulated")
+    print(f"{variant} digits ({ab or 'default'}): 64 lanes, {bad} mismatches, {steps} wave-instructions emulated")
     return bad
 
 
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'nadicb':
         sys.exit(1 if nadicb_selftest(waves=int(sys.argv[2]) if len(sys.argv) > 2 else 1) else 0)
-    if len(sys.argv) > 1 and sys.argv[1] == 'm37':
-        sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None) else 0)
+    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t'):
+        sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None, variant=sys.argv[1]) else 0)
     elif len(sys.argv) > 1:                   # e.g. 211: wave 0 takes a second batch (the grid-stride loop)
         selftest(ntests=int(sys.argv[1]), count0=int(sys.argv[1]))
     else:
