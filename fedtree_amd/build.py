@@ -69,6 +69,10 @@ def build_kernels():
     # its four-tile body (product 2 of the reductions without its fifth M-tile): pseudo-variant 1237
     kernels.append((1237, "fthe_padic_m37t", "padic_m37t",
                     lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37t", top_est=True)))
+    # the four-tile body on product 1's operand shifted by 8 bytes (15 instead of 19 product-1 tiles): 1337
+    kernels.append((1337, "fthe_padic_m37s", "padic_m37s",
+                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37s", top_est=True,
+                                                          q1_shift=gen_padic_mfma.Q1_SHIFT)))
     # the n-adic four-lane kernel of the public-key encrypt (base-n digits of 76 limbs): pseudo-variant 2076
     kernels.append((2076, "fthe_nadic_q76", "nadic_q76", lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_q76")))
     # its Montgomery form (LSB-first reductions, no quotient estimates): pseudo-variant 2176

@@ -33,9 +33,11 @@ Ops: those of gen_padic.py except the fixed-base table ops (LOADXGD / MULGD), wh
 fthe_padic_k37:  0 END, 1 LOADX, 2 STOREX, 3 SQR, 4 MUL, 22 LOADP, 23 STOREP.
 ctx: [-P limbs (K, int32) ...] as for fthe_padic_k37, and the LDS tile image at byte 512 (20 KB).
 
-Two bodies: fthe_padic_m37 (the default output, above) and fthe_padic_m37t (top_est=True, for P of at most
+Three bodies: fthe_padic_m37 (the default output, above); fthe_padic_m37t (top_est=True, for P of at most
 TOPEST_MAX_BITS bits), whose product 2 in the reductions of SQR / MUL runs four M-tiles and takes r's bits above
-1015 from product 1's fraction (see gen_padic_mfma's docstring); its ctx also holds Pt = P >> 1000 at byte PT_OFF.
+1015 from product 1's fraction (see gen_padic_mfma's docstring), its ctx also holding Pt = P >> 1000 at byte PT_OFF;
+and fthe_padic_m37s (top_est=True, q1_shift=8), the same with product 1's operand fed 8 bytes later, which empties
+the four tiles with m - k = 1: 15 product-1 tiles, and the image of padic_tiles::build(P, 128, 8).
 """
 import os
 import sys
@@ -103,8 +105,13 @@ TILE_D1 = (-3, -2, -1, 0, 1)    # product-1 Toeplitz tiles (k <= 3) by m - k; th
 TILE_D2 = (0, 1, 2, 3)          # product-2: k = 0 for m = 0..4 (tiles 10..14), then Toeplitz (k >= 1) by m - k
 
 
-def tile_index(prod, m, k):
+def tile_index(prod, m, k, q1_shift=0):
+    """q1_shift (fthe_padic_m37s): no product-1 tile with m - k = 1; tile (0, 0), whose first q1_shift columns are
+    the operand's pad, takes that slot (it is the only one formed with k = 0)"""
     if prod == 1:
+        if q1_shift and k == 0:
+            assert m == 0
+            return 4
         return TILE_D1.index(m - k) if k <= 3 else 5 + m
     return 10 + m if k == 0 else 15 + TILE_D2.index(m - k)
 
@@ -117,8 +124,16 @@ PT_SHIFT = 1000
 TOPEST_C = 128 << 8             # the window constant c = 128 units of 2^1008, in units of 2^1000
 
 
-def gen_padic_mfma(name: str, top_est: bool = False) -> str:
-    """top_est: the four-tile body.  In the reductions of SQR and MUL product 2 runs M-tiles 0..3 only (K-blocks
+Q1_SHIFT = 8                    # fthe_padic_m37s: q1's byte i is fed at K index i + Q1_SHIFT
+
+
+def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
+    """q1_shift = 8 (with top_est: fthe_padic_m37s): product 1's operand starts two dwords later -- q1 in D[2..35],
+    the constant dword (digits 1 and 16 c, K indices 144 and 145) in D[36] -- so that A1[s][i] = mu'[s - i + 8] and
+    the sub-diagonal tiles (m - k = 1: s - i + 8 >= 137, above mu's last digit 133) are zero and are not formed: 15
+    tiles instead of 19, every column sum unchanged.  The A columns of K indices 0..7 and 146..159 are
+    zero, so D[0], D[1] and D[37..39] are never written: whatever they hold meets zeros.
+    top_est: the four-tile body.  In the reductions of SQR and MUL product 2 runs M-tiles 0..3 only (K-blocks
     0..3 of the operand: 20 MFMAs instead of 30), which give r mod 2^1016 exactly, and bits 1016.. of r follow from
     f = frac(N / 2^1064), the guard bits product 1's fold passes through anyway: r = P (f + e) with
     0 <= e P < 2^1015, so with E = floor(f32 Pt / 2^32) (units of 2^1000) and b = bits 1008..1015 of r,
@@ -129,6 +144,8 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
     plain residue below 3 P^2 (x1 = its quotient); its own reduction keeps the five-tile product 2."""
     K, B = 37, 28
     MASK = (1 << B) - 1
+    assert q1_shift in (0, Q1_SHIFT) and not (q1_shift and (LDSX or S1_LO != 128))
+    QD = q1_shift // 4                           # the operand's first dword
     # ---- VGPR plan ---------------------------------------------------------
     V_TID, V_GOFF = 0, 1
     VA = (2, 6, 10)                              # A-tile buffers v[2:5], v[6:9], v[10:13] (ACC is free)
@@ -330,11 +347,12 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
     SMASK = "s35"                               # 0x0fffffff (v_bfi_b32 operand)
     S2MASK, S3MASK, S4MASK = "s76", "s77", "s78"  # KARA: 2, 3, 4 x 0x0fffffff
 
-    def orpack(limbs, shift_bits, ndw, xor_masks, lead_one=False, norm0=False, pre=()):
+    def orpack(limbs, shift_bits, ndw, xor_masks, lead_one=False, norm0=False, pre=(), d0=0):
         """normalised 28-bit limbs (limb t at bit 28 t + shift_bits) -> dwords D[0..ndw-1] XOR xor_masks[w],
         each dword from the (at most two) limbs it overlaps: no carry chain.  lead_one: byte 0 is the
         constant digit 1 (shift_bits = 8).  norm0: limb 0 may hold a bit 28 (masked off here).  pre: the
-        limbs already XORed with pat(t) (PREXOR); only the flips they do not carry are applied here."""
+        limbs already XORed with pat(t) (PREXOR); only the flips they do not carry are applied here.  d0: the
+        dwords go to D[d0 ..]."""
         n = len(limbs)
         pre = set(pre)
 
@@ -351,7 +369,7 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
             return m
         xor_masks = [xor_masks[w] ^ carried(w) for w in range(ndw)]
         for w in range(ndw):
-            d = D[w]
+            d = D[w + d0]
             if lead_one and w == 0:
                 e(f'  v_lshl_or_b32 {d}, {limbs[0]}, 8, 1')
             else:
@@ -405,7 +423,7 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
 
     def rd(prod, m, k, n):
         b_ = VA[n % 3]
-        e(f'  ds_read_b128 v[{b_}:{b_ + 3}], v{V_LDS} offset:{1024 * tile_index(prod, m, k)}')
+        e(f'  ds_read_b128 v[{b_}:{b_ + 3}], v{V_LDS} offset:{1024 * tile_index(prod, m, k, q1_shift)}')
 
     def prefetch(prod, m, ks):
         """the first two A-tile reads of M-tile m (issued while the lane still has VALU work)"""
@@ -695,7 +713,7 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
             ch.column(s_, r_)
             i += 1
 
-    P1_TILES = [(1, m, [k for k in range(5) if m - k <= 1]) for m in range(5)]
+    P1_TILES = [(1, m, [k for k in range(5) if m - k <= (0 if q1_shift else 1)]) for m in range(5)]
     P2_TILES = [(2, m, [k for k in range(5) if m >= k]) for m in range(5)]
     assert P1_TILES[0][2][0] != 4 and P2_TILES[0][2][0] != 4      # LDSX: see swap_operands
 
@@ -716,11 +734,13 @@ def gen_padic_mfma(name: str, top_est: bool = False) -> str:
             pre_in = PREXOR
         if not prefetched:
             prefetch(*P1_TILES[0])
-        orpack(Tl[K - 1:2 * K], 0, 34, [0x80808080] * 34, norm0=True, pre=range(1, K + 1) if pre_in else ())
-        e(f'  v_bfe_u32 {D[34]}, {Tl[K - 1]}, 28, 1')              # c = bit 28 of q1[0] -> digit 16 c at byte 137
-        e(f'  v_lshl_or_b32 {D[34]}, {D[34]}, 12, 1')               # and the constant digit 1 at byte 136
-        for w in range(35, 40):
-            e(f'  v_mov_b32_e32 {D[w]}, 0')
+        orpack(Tl[K - 1:2 * K], 0, 34, [0x80808080] * 34, norm0=True, pre=range(1, K + 1) if pre_in else (), d0=QD)
+        DC = D[34 + QD]
+        e(f'  v_bfe_u32 {DC}, {Tl[K - 1]}, 28, 1')                  # c = bit 28 of q1[0] -> digit 16 c at byte 137
+        e(f'  v_lshl_or_b32 {DC}, {DC}, 12, 1')                     # and the constant digit 1 at byte 136
+        if not q1_shift:                                            # q1_shift: the pads meet zero A columns
+            for w in range(35, 40):
+                e(f'  v_mov_b32_e32 {D[w]}, 0')
         swap_operands()
         if dw is None:
             # chunk -1 is bits 1036..1063 of N: f32 = its 28 bits over four zeros
@@ -1215,7 +1235,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument('--name', default='fthe_padic_m37')
     ap.add_argument('--top-est', action='store_true', help='the four-tile body (fthe_padic_m37t)')
+    ap.add_argument('--q1-shift', type=int, default=0, help='8 with --top-est: the shifted operand (fthe_padic_m37s)')
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:
-        f.write(gen_padic_mfma(a.name, top_est=a.top_est))
+        f.write(gen_padic_mfma(a.name, top_est=a.top_est, q1_shift=a.q1_shift))

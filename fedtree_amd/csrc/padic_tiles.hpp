@@ -18,7 +18,7 @@
 // Tile t (1 KB): lane l's 16 bytes at l * 16 are row r = l & 31, digits i = 16 (l >> 5) + j (the
 // v_mfma_i32_32x32x32_i8 A map).  Order: product 1 Toeplitz m - k = -3..1 (k <= 3), product 1 k = 4 for
 // m = 0..4, product 2 k = 0 for m = 0..4, product 2 Toeplitz m - k = 0..3 (k >= 1).  19 tiles, padded to
-// 20 KB (the kernel's LDS fill).
+// 20 KB (the kernel's LDS fill).  build(P, 128, 8) is the image of fthe_padic_m37s (see build).
 #pragma once
 #include <gmp.h>
 #include <cstdint>
@@ -26,7 +26,7 @@
 
 namespace padic_tiles {
 
-constexpr int kTiles = 19, kImageBytes = 20 * 1024, kS1Lo = 128, kNq1 = 136, kConst1 = 136, kNq3 = 132;
+constexpr int kTiles = 19, kImageBytes = 20 * 1024, kS1Lo = 128, kNq1 = 136, kConst1 = 136, kNq3 = 132, kQShift = 8;
 
 // n balanced base-256 digits of x >= 0; false if they do not hold x
 inline bool balanced(const mpz_t x, int n, std::vector<int> &d) {
@@ -56,11 +56,17 @@ inline void offset_sum(mpz_t out, const mpz_t x, int n) {
     mpz_clear(g);
 }
 
-// the image for P (K = 37 digits: P of 1009..1030 bits); empty on failure.  s1lo: product 1's first column
-inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo) {
+// the image for P (K = 37 digits: P of 1009..1030 bits); empty on failure.  s1lo: product 1's first column.
+// qshift = kQShift (fthe_padic_m37s, s1lo = 128): product 1's operand byte i is fed at digit index i + 8, so
+// A1[s][i] = mu'[s - i + 8] for 8 <= i < 144, the constant digits sit at 144 and 145, and the columns i < 8 (the
+// operand's pad) and i > 145 are zero.  The tiles with m - k = 1 are then zero (s - i + 8 >= 137 > 133, mu's last
+// digit) and leave the image; tile (0, 0), which holds the pad columns and so is no instance of the m - k = 0
+// Toeplitz tile, takes their slot (tile 4).  Product 2's tiles are the same.
+inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo, int qshift = 0) {
     std::vector<uint8_t> img;
     if (mpz_sizeinbase(P, 2) < 1009 || mpz_sizeinbase(P, 2) > 1030) return img;
     if (s1lo != 112 && s1lo != 128) return img;
+    if (qshift != 0 && (qshift != kQShift || s1lo != 128)) return img;
     mpz_t mu, c, b;
     mpz_inits(mu, c, b, nullptr);
     mpz_set_ui(mu, 1);
@@ -81,6 +87,8 @@ inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo) {
     if (!ok) return img;
     g2.resize(130);
     auto a1 = [&](int s, int i) -> int {
+        i -= qshift;
+        if (i < 0) return 0;
         if (i == kConst1) return (s >= s1lo && s < s1lo + 160) ? g1[s - s1lo] : 0;
         if (i == kConst1 + 1) {                 // 16 c, c = bit 28 of q1's lowest limb: mu' shifted 3 bytes
             int j = s - 3;
@@ -105,7 +113,12 @@ inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo) {
             }
         }
     };
-    for (int d = -3; d <= 1; d++) tile(1, s1lo, d >= 0 ? d : 0, d >= 0 ? 0 : -d);
+    if (qshift) {
+        for (int d = -3; d <= 0; d++) tile(1, s1lo, d + 3, 3);
+        tile(1, s1lo, 0, 0);
+    } else {
+        for (int d = -3; d <= 1; d++) tile(1, s1lo, d >= 0 ? d : 0, d >= 0 ? 0 : -d);
+    }
     for (int m = 0; m < 5; m++) tile(1, s1lo, m, 4);
     for (int m = 0; m < 5; m++) tile(2, 0, m, 0);
     for (int d = 0; d <= 3; d++) tile(2, 0, d + 1, 1);

@@ -4,6 +4,8 @@
 #   bash tools/m37_ab.sh TAG V1 V2 [V3 ...]     (tools/bin/m37_V.hsaco; lanes: M37_LANES, default 393216)
 # A variant named t or t_* holds the four-tile body fthe_padic_m37t (gen_padic_mfma.py --top-est), so
 #   bash tools/m37_ab.sh TAG base t     runs m37 and m37t round-robin in one series.
+# A variant named s or s_* holds fthe_padic_m37s (--top-est --q1-shift 8) and reads the shifted tile image:
+#   bash tools/m37_ab.sh TAG t s
 T=${1:?tag}; shift
 N=${M37_LANES:-393216}
 mkdir -p gpurun_out
@@ -15,6 +17,7 @@ for r in 1 2 3; do
     export M37_S1LO=128; [[ $v == *s1lo112* ]] && export M37_S1LO=112
     # the harness looks up M37_KERNEL, when set, in place of the kernel named on its command line
     unset M37_KERNEL; [[ $v == t || $v == t_* ]] && export M37_KERNEL=fthe_padic_m37t
+    export M37_QSHIFT=0; [[ $v == s || $v == s_* ]] && export M37_KERNEL=fthe_padic_m37s M37_QSHIFT=8
     M37_BLOCK=$blk timeout -k 10 120 tools/bin/test_padic tools/bin/m37_$v.hsaco $N 0 fthe_padic_m37 > gpurun_out/${T}_one.json
     rc=$?
     # timing-only variants (nomfma, noswap, nonop: wrong results by design) may report bad lanes (rc 1)

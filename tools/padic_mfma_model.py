@@ -40,6 +40,9 @@ core), the same chunk accumulation (64-bit, arithmetic shifts) and the same clam
 bound (int32 column sums, 64-bit accumulators, digits < 5P).  It also builds the A tiles in the lane
 order of the LDS image that the kernel reads (tile_image), which the host code must reproduce.
 
+fthe_padic_m37s feeds product 1's operand 8 digit positions later (MfmaKey(P, q_shift=8)): the same column sums
+from 15 tiles instead of 19 (see MfmaKey).
+
 Run:  python tools/padic_mfma_model.py [seed] [trials]
 """
 import os
@@ -87,10 +90,20 @@ def balanced(x, n):
     return d
 
 
+Q1_SHIFT = 8                     # fthe_padic_m37s: q1's byte i is fed at digit index i + 8 (two dwords later)
+
+
 class MfmaKey(pm.PadicKey):
-    def __init__(self, P, s1_lo=S1_LO):
+    """q_shift (fthe_padic_m37s: Q1_SHIFT): product 1's operand starts q_shift digits later, A1'[s][i + q_shift] =
+    A1[s][i] with zero columns below q_shift (the operand's pad), so every column sum is the same and the tiles
+    with m - k = 1 hold only mu' digits from index 137 on: zero, since mu < 2^1064 ends at digit 133.  Any shift
+    (a multiple of 4 up to 20) is modelled, so that the tests can show that 4 does not empty those tiles."""
+
+    def __init__(self, P, s1_lo=S1_LO, q_shift=0):
         super().__init__(P, K)
         assert s1_lo in (112, 128)                          # 112: the window and bias of rounds 2-6
+        assert q_shift == 0 or (s1_lo == 128 and q_shift % 4 == 0 and 0 < q_shift <= 160 - CONST1 - 2)
+        self.q_shift = q_shift
         self.s1_lo, self.bias_bits = s1_lo, 8 * s1_lo + 22
         mu = pm.value(self.mu)
         self.mu_d = balanced(mu, 135)                       # mu < 2^1063: 134 digits + a carry digit
@@ -103,6 +116,9 @@ class MfmaKey(pm.PadicKey):
 
     # A[s][i] of the two products (s: output column, i: B digit index)
     def a1(self, s, i):
+        i -= self.q_shift                       # the digit index of the unshifted layout; the pad columns are zero
+        if i < 0:
+            return 0
         if i == CONST1:
             return self.g1[s - self.s1_lo] if self.s1_lo <= s < self.s1_lo + 160 else 0
         if i == CONST1 + 1:                     # 16 c for the bit 28 of q1's lowest limb (< 2^29)
@@ -121,17 +137,40 @@ class MfmaKey(pm.PadicKey):
         j = s - i
         return self.P_d[j] if 0 <= j < len(self.P_d) else 0
 
+    def d1_max(self):
+        """product 1 forms the tiles with m - k <= d1_max"""
+        return 0 if self.q_shift else 1
+
+    def tiles1(self):
+        """product 1's tiles as the kernel forms them: {m: [k ...]}"""
+        return {m: [k for k in range(5) if m - k <= self.d1_max()] for m in range(5)}
+
+    def tile1_slot(self, m, k):
+        """the image tile that the kernel reads for product 1's tile (m, k) (gen_padic_mfma.tile_index)"""
+        if k == 4:
+            return 5 + m
+        if self.q_shift and k == 0:
+            assert m == 0                       # the pad columns: no instance of the m - k = 0 Toeplitz tile
+            return 4
+        return TILE_D1.index(m - k)
+
     def check_skipped_tiles(self):
-        """the kernel forms only tiles (m, k) with m - k <= 1 (product 1) and m >= k (product 2): every
-        other tile of the A matrices must be zero (and the Toeplitz tiles equal along m - k)"""
+        """the kernel forms only tiles (m, k) with m - k <= 1 (product 1; m - k <= 0 under q_shift) and m >= k
+        (product 2): every other tile of the A matrices must be zero, and the tiles that share an image slot
+        equal"""
         for m in range(5):
             for k in range(5):
                 for r in range(32):
                     for i in range(32 * k, 32 * k + 32):
-                        if m - k > 1:
+                        if m - k > self.d1_max():
                             assert self.a1(self.s1_lo + 32 * m + r, i) == 0, (m, k)
                         if m < k:
                             assert self.a2(32 * m + r, i) == 0, (m, k)
+        slots = {}
+        for m, ks in self.tiles1().items():
+            for k in ks:
+                t = [self.a1(self.s1_lo + 32 * m + r, 32 * k + i) for r in range(32) for i in range(32)]
+                assert slots.setdefault(self.tile1_slot(m, k), t) == t, (m, k)
         for s in range(S1_TOP, self.s1_lo + 160):           # the rows of M-tile 4 that the fold leaves out
             assert all(self.a1(s, i) == 0 for i in range(160)), s
 
@@ -147,9 +186,15 @@ class MfmaKey(pm.PadicKey):
                 r, h = l & 31, l >> 5
                 for j in range(16):
                     out.append(fn(s_base + 32 * m + r, 32 * k + 16 * h + j) & 255)
-        for d in TILE_D1:                       # (m, k) = (d + 3, 3) is one of its instances... any will do
-            m, k = (d, 0) if d >= 0 else (0, -d)
-            tile(self.a1, self.s1_lo, m, k)
+        if self.q_shift:                        # Toeplitz d = -3..0 (k = 3), then tile (0, 0) in the slot of d = 1
+            assert self.q_shift == Q1_SHIFT
+            for d in TILE_D1[:4]:
+                tile(self.a1, self.s1_lo, d + 3, 3)
+            tile(self.a1, self.s1_lo, 0, 0)
+        else:
+            for d in TILE_D1:                   # (m, k) = (d + 3, 3) is one of its instances... any will do
+                m, k = (d, 0) if d >= 0 else (0, -d)
+                tile(self.a1, self.s1_lo, m, k)
         for m in range(5):
             tile(self.a1, self.s1_lo, m, 4)
         for m in range(5):
@@ -196,16 +241,23 @@ def orpack(limbs_, shift_bits, ndw):
     return [(val >> (32 * w)) & 0xFFFFFFFF for w in range(ndw)]
 
 
-def columns1(key, q1):
-    """the int32 column sums s1_lo .. S1_TOP - 1 of product 1, and Pi = q1 mu"""
+def columns1(key, q1, pad=None):
+    """the int32 column sums s1_lo .. S1_TOP - 1 of product 1 over the tiles the kernel forms (key.tiles1()), and
+    Pi = q1 mu.  pad (q_shift): a function giving the dwords the kernel leaves undefined (the operand's pad and
+    the dwords above the constant one); default 0"""
     c = q1[0] >> B
     assert c in (0, 1)
-    dw = orpack([q1[0] & MASK] + list(q1[1:]), 0, 34) + [1 | (c << 12), 0, 0, 0, 0, 0]
-    dig = digits_of(dw, [0x80808080] * 34 + [0] * 6)
-    assert dig[CONST1] == 1 and dig[CONST1 + 1] == 16 * c
+    qd = key.q_shift // 4
+    fill = pad or (lambda: 0)
+    dw = [fill() for _ in range(qd)] + orpack([q1[0] & MASK] + list(q1[1:]), 0, 34) + [1 | (c << 12)]
+    dw += [fill() if qd else 0 for _ in range(40 - len(dw))]
+    dig = digits_of(dw, [0] * qd + [0x80808080] * 34 + [0] * (6 - qd))
+    assert dig[CONST1 + key.q_shift] == 1 and dig[CONST1 + 1 + key.q_shift] == 16 * c
     col = {}
+    tiles = key.tiles1()
     for s in range(key.s1_lo, S1_TOP):
-        col[s] = s32(sum(key.a1(s, i) * dig[i] for i in range(160) if dig[i]))
+        ks = tiles[(s - key.s1_lo) // 32]
+        col[s] = s32(sum(key.a1(s, i) * dig[i] for k in ks for i in range(32 * k, 32 * k + 32) if dig[i]))
     Pi = pm.value(q1) * pm.value(key.mu)
     N = sum(v << (8 * s) for s, v in col.items())
     assert Pi - (1 << (key.bias_bits + 1)) < N < Pi and key.bias_bits + 1 <= QBIT, "Pi - 2^1064 < N < Pi"
@@ -450,7 +502,7 @@ def main():
     for t in range(trials):
         bits = rng.choice([1009, 1010, 1023, 1024, 1024, 1029, 1030])
         P = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
-        key = MfmaKey(P)
+        key = MfmaKey(P, q_shift=Q1_SHIFT if t % 2 else 0)      # both layouts give the same column sums
         assert len(key.tile_image()) == 19 * 1024
         key.check_skipped_tiles()
         P2 = P * P
@@ -488,7 +540,7 @@ def main():
     for t in range(trials):
         bits = rng.choice([1009, 1010, 1023, 1024, 1024, 1026, TOPEST_MAX_BITS])
         P = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
-        key = MfmaKey(P)
+        key = MfmaKey(P, q_shift=Q1_SHIFT if t % 2 else 0)      # fthe_padic_m37s / fthe_padic_m37t
         P2 = P * P
         top = TOPEST_DIGIT * P - 1
         for x0v, x1v in ((top, top), (1, 0), (0, 1), (P - 1, P - 1), (2 * P - 1, 2 * P - 1),

@@ -4,6 +4,7 @@
 //        bring-up programs: 2: LOADP; STOREP (c < P^2), 3: LOADP; SQR 1; STOREP, 4: LOADP; SQR 1; MUL IN; STOREP
 //        kernel: fthe_padic_k37 (default), fthe_padic_m37 (gen_padic_mfma.py: ctx carries the LDS tile image) or
 //        fthe_padic_m37t (its four-tile body: ctx also carries Pt = P >> 1000 at word 100)
+//        fthe_padic_m37s (the four-tile body on the shifted operand: M37_QSHIFT=8 selects its tile image)
 // Checks sampled lanes against GMP's mpz_powm and prints the launch time and products per second.
 #include <hip/hip_runtime.h>
 #include <gmp.h>
@@ -96,7 +97,9 @@ int main(int argc, char **argv) {
     mpz_fdiv_q_2exp(t, P, 1000); ctx[100] = (uint32_t)mpz_get_ui(t);     // Pt (gen_padic_mfma.py PT_OFF = 400)
     {
         // M37_S1LO=112: the image of code objects generated with the s1lo112 switch (product 1 from column 112)
-        std::vector<uint8_t> img = padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo);
+        // M37_QSHIFT=8: the image of fthe_padic_m37s (product 1's operand shifted by 8 bytes)
+        std::vector<uint8_t> img = padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo,
+                                                      getenv("M37_QSHIFT") ? atoi(getenv("M37_QSHIFT")) : 0);
         if (img.empty()) { printf("tile image failed\n"); return 2; }
         memcpy(ctx.data() + 128, img.data(), img.size());
     }

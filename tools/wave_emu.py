@@ -9,7 +9,7 @@ workgroup is emulated wave by wave: every wave up to its s_barrier, then each wa
 waves share only what they wrote before the barrier).
 
   python tools/wave_emu.py         (self-test: 16 random adds mod n^2 and edge cases vs Python integers)
-  python tools/wave_emu.py m37     (one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
+  python tools/wave_emu.py m37     (m37t, m37s: the other bodies; one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
 """
 import os
 import random
@@ -644,12 +644,16 @@ def parse(asm):
     return prog, labels
 
 
-def run_workgroup(asm, lds_bytes, waves, mem, kernarg_addr, wg, nvgpr, finish=None):
-    """finish: the waves to run past their first barrier (default all)"""
+def run_workgroup(asm, lds_bytes, waves, mem, kernarg_addr, wg, nvgpr, finish=None, junk=None):
+    """finish: the waves to run past their first barrier (default all); junk: {vgpr: [64 lane values]} held at the
+    start instead of zeros (registers the kernel reads without having written them)"""
     prog, labels = parse(asm)
     lds = bytearray(lds_bytes)
     ws = [Wave(prog, labels, lds, mem, {0: kernarg_addr & M32, 1: kernarg_addr >> 32, 2: wg}, 64 * w, nvgpr)
           for w in range(waves)]
+    for w in ws:
+        for r, vals in (junk or {}).items():
+            w.v[r] = [x & M32 for x in vals]
     for w in ws:
         w.run()
     for i, w in enumerate(ws):
@@ -800,30 +804,34 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
 
 
 def _m37_asm(gm, variant):
-    """the kernel text of a variant: 'm37' (fthe_padic_m37) or 'm37t' (fthe_padic_m37t, the four-tile product 2)"""
-    assert variant in ('m37', 'm37t')
-    return gm.gen_padic_mfma('fthe_padic_' + variant, top_est=variant == 'm37t')
+    """the kernel text of a variant: 'm37' (fthe_padic_m37), 'm37t' (fthe_padic_m37t, the four-tile product 2) or
+    'm37s' (fthe_padic_m37s: m37t with product 1's operand shifted by 8 bytes, 15 tiles)"""
+    assert variant in ('m37', 'm37t', 'm37s')
+    return gm.gen_padic_mfma('fthe_padic_' + variant, top_est=variant != 'm37',
+                             q1_shift=gm.Q1_SHIFT if variant == 'm37s' else 0)
 
 
 def _m37_ctx(gm, mm, P, s1_lo, variant):
-    """the key context: -P limbs, Pt = P >> 1000 (m37t), the tile image"""
+    """the key context: -P limbs, Pt = P >> 1000 (m37t, m37s), the tile image (m37s: the shifted layout)"""
     K, B = 37, 28
     ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
     for j in range(K):                                           # -P limbs (int32)
         ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
-    if variant == 'm37t':
+    if variant != 'm37':
         assert P.bit_length() <= gm.TOPEST_MAX_BITS == mm.TOPEST_MAX_BITS
         ctx[gm.PT_OFF:gm.PT_OFF + 4] = (P >> gm.PT_SHIFT).to_bytes(4, 'little')
-    img = mm.MfmaKey(P, s1_lo=s1_lo).tile_image()
+    assert gm.Q1_SHIFT == mm.Q1_SHIFT
+    img = mm.MfmaKey(P, s1_lo=s1_lo, q_shift=mm.Q1_SHIFT if variant == 'm37s' else 0).tile_image()
     ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
     return ctx
 
 
-def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None):
+def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None, junk_pads=False):
     """wave 0 of fthe_padic_m37 (one workgroup of 256 lanes, 4 waves fill the LDS tile image, wave 0 runs on):
     LOADP x; STOREX t; SQR 1; MUL t; STOREP -> x^3 mod P^2 (< 6 P^2), against Python integers on its 64 lanes
     (x < P^2: 0, 1, P - 1, P, P^2 - 1, the values of extra and random).  ab: a generator switch string
-    (FTHE_GEN_M37_AB).  variant: 'm37' or 'm37t'.  P: the modulus (default: random of `bits` bits)."""
+    (FTHE_GEN_M37_AB).  variant: 'm37', 'm37t' or 'm37s'.  P: the modulus (default: random of `bits` bits).
+    junk_pads: product 1's operand dwords 0, 1 and 37..39 (m37s never writes them) start as random words."""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
     sys.path.insert(0, here)
@@ -870,7 +878,8 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None):
         (L * 4).to_bytes(4, 'little') + (S * L * 4).to_bytes(4, 'little') + L.to_bytes(4, 'little') + \
         (1).to_bytes(4, 'little') + bytes(128)
     mem.alloc(karg, KA)
-    steps = run_workgroup(asm, lds_bytes, 4, mem, KA, 0, nv, finish=(0,))
+    junk = {60 + w: [rng.getrandbits(32) for _ in range(64)] for w in (0, 1, 37, 38, 39)} if junk_pads else None
+    steps = run_workgroup(asm, lds_bytes, 4, mem, KA, 0, nv, finish=(0,), junk=junk)
     bad = 0
     for g_ in range(64):
         got = 0
@@ -915,7 +924,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
     P2 = P * P
     K, S, L, B = 37, 74, 256, 28
     MASK = (1 << B) - 1
-    nd = mm.TOPEST_DIGIT if variant == 'm37t' else 5
+    nd = mm.TOPEST_DIGIT if variant != 'm37' else 5
     top = nd * P - 1                                             # the largest digit
     allones = (1 << (B * (K - 1))) - 1                           # limbs 0..35 = 2^28 - 1
     big = allones + (((top - allones) >> (B * (K - 1))) << (B * (K - 1)))
@@ -965,7 +974,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'nadicb':
         sys.exit(1 if nadicb_selftest(waves=int(sys.argv[2]) if len(sys.argv) > 2 else 1) else 0)
-    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t'):
+    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s'):
         sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None, variant=sys.argv[1]) else 0)
     elif len(sys.argv) > 1:                   # e.g. 211: wave 0 takes a second batch (the grid-stride loop)
         selftest(ntests=int(sys.argv[1]), count0=int(sys.argv[1]))
