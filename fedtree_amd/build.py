@@ -73,6 +73,9 @@ def build_kernels():
     kernels.append((1337, "fthe_padic_m37s", "padic_m37s",
                     lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37s", top_est=True,
                                                           q1_shift=gen_padic_mfma.Q1_SHIFT)))
+    # the four-tile body with product 1 fed q1's limbs as they lie (no repack before product 1): 1437
+    kernels.append((1437, "fthe_padic_m37l", "padic_m37l",
+                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37l", top_est=True, limb_op=True)))
     # the n-adic four-lane kernel of the public-key encrypt (base-n digits of 76 limbs): pseudo-variant 2076
     kernels.append((2076, "fthe_nadic_q76", "nadic_q76", lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_q76")))
     # its Montgomery form (LSB-first reductions, no quotient estimates): pseudo-variant 2176

@@ -44,7 +44,7 @@ using namespace fthe;
 
 namespace {
 
-constexpr int MAX_VARIANTS = 12;
+constexpr int MAX_VARIANTS = 13;
 // s80: four lanes per element mod p^2 / q^2 of Paillier-2048 (small-batch decrypt latency);
 // 1000 + K: the P-adic exponentiation kernels mod P^2 (gen_padic.py, digits of K limbs, slots of 2K
 // limbs; the "S" here only names the variant): K = 37 runs on the s74 slots of Paillier-2048,
@@ -54,19 +54,23 @@ constexpr int MAX_VARIANTS = 12;
 // 1237: its four-tile body fthe_padic_m37t (gen_padic_mfma.py top_est) for P of at most kPadicTopBits bits; its
 // launches are also counted under 1137 (fthe_prof_read), so 1237 only tells which body ran;
 // 1337: fthe_padic_m37s, the four-tile body with product 1's operand shifted by 8 bytes (gen_padic_mfma.py q1_shift:
-// 15 instead of 19 product-1 tiles), the default for the same P; its launches are also counted under 1237 and 1137;
+// 15 instead of 19 product-1 tiles); its launches are also counted under 1237 and 1137;
+// 1437: fthe_padic_m37l, the four-tile body with product 1 fed q1's radix-2^28 limbs as they lie (gen_padic_mfma.py
+// limb_op: no repack before product 1; a 24 KB tile image, padic_tiles::build_limb), the default for the same P; its
+// launches are also counted under 1337, 1237 and 1137;
 // 2000 + 76: the n-adic four-lane kernel (gen_nadic.py, base-n digits of 76 limbs) on the s152 slots;
 // 2100 + 76: its Montgomery form (gen_nadic.py mont: LSB-first reductions, no quotient estimates)
 // 2200 + 76: its matrix-core Barrett form (gen_nadicb.py: the products on the VALU, both Barrett reductions by n
 // on i8 MFMA; workgroups of kNbWaves waves, n of 2041..2048 bits)
 constexpr int kPadicS = 1037, kPadicK = 37, kPadicSmallK = 19, kNadicS = 2076, kPadicMfmaS = 1137,
-              kNadicMontS = 2176, kNadicBarS = 2276, kPadicMfmaTS = 1237, kPadicMfmaSS = 1337;
+              kNadicMontS = 2176, kNadicBarS = 2276, kPadicMfmaTS = 1237, kPadicMfmaSS = 1337,
+              kPadicMfmaLS = 1437;
 // fthe_padic_m37t: the widest P (TOPEST_MAX_BITS of gen_padic_mfma.py), Pt = P >> kPadicPtShift at ctx word kPadicPtWord
 constexpr int kPadicTopBits = 1027, kPadicPtShift = 1000, kPadicPtWord = 100;
 const Shape kVariants[MAX_VARIANTS] = {{37, 28, 1}, {74, 28, 1}, {152, 27, 4}, {80, 27, 4},
                                        {1000 + kPadicK, 28, 1}, {1000 + kPadicSmallK, 28, 1}, {kNadicS, 27, 4},
                                        {kPadicMfmaS, 28, 1}, {kNadicMontS, 27, 4}, {kNadicBarS, 27, 4},
-                                       {kPadicMfmaTS, 28, 1}, {kPadicMfmaSS, 28, 1}};
+                                       {kPadicMfmaTS, 28, 1}, {kPadicMfmaSS, 28, 1}, {kPadicMfmaLS, 28, 1}};
 constexpr Shape kLatShape{80, 27, 4};
 constexpr int kAddbBlob = 3152;           // fthe_addb_q152's code object in gen/montprog_blobs.h
 
@@ -579,6 +583,7 @@ extern "C" int fthe_ctx_create(int device, fthe_ctx **out) {
         if (kVariants[i].S > 2200) snprintf(name, sizeof name, "fthe_nadic_b%d", kVariants[i].S - 2200);
         else if (kVariants[i].S > 2100) snprintf(name, sizeof name, "fthe_nadic_m%d", kVariants[i].S - 2100);
         else if (kVariants[i].S > 2000) snprintf(name, sizeof name, "fthe_nadic_q%d", kVariants[i].S - 2000);
+        else if (kVariants[i].S > 1400) snprintf(name, sizeof name, "fthe_padic_m%dl", kVariants[i].S - 1400);
         else if (kVariants[i].S > 1300) snprintf(name, sizeof name, "fthe_padic_m%ds", kVariants[i].S - 1300);
         else if (kVariants[i].S > 1200) snprintf(name, sizeof name, "fthe_padic_m%dt", kVariants[i].S - 1200);
         else if (kVariants[i].S > 1100) snprintf(name, sizeof name, "fthe_padic_m%d", kVariants[i].S - 1100);
@@ -713,12 +718,16 @@ extern "C" int fthe_prof_read(fthe_ctx *c, double *kernel_ms, double *launches, 
             etot += ms; en += 1;
             c->var_ms[c->prof_vi[i]] += ms; c->var_n[c->prof_vi[i]] += 1;
             const int vs = kVariants[c->prof_vi[i]].S;            // the same kernel family: read as 1137 too,
-            if (vs == kPadicMfmaTS || vs == kPadicMfmaSS) {       // and the shifted four-tile body as 1237
-                const int vm = variant_index(kPadicMfmaS);
+            if (vs == kPadicMfmaTS || vs == kPadicMfmaSS || vs == kPadicMfmaLS) {   // and the later four-tile
+                const int vm = variant_index(kPadicMfmaS);                         // bodies as their ancestors
                 c->var_ms[vm] += ms; c->var_n[vm] += 1;
             }
-            if (vs == kPadicMfmaSS) {
+            if (vs == kPadicMfmaSS || vs == kPadicMfmaLS) {
                 const int vt = variant_index(kPadicMfmaTS);
+                c->var_ms[vt] += ms; c->var_n[vt] += 1;
+            }
+            if (vs == kPadicMfmaLS) {
+                const int vt = variant_index(kPadicMfmaSS);
                 c->var_ms[vt] += ms; c->var_n[vt] += 1;
             }
             eiv.emplace_back(t0, (double)t0 + ms);
@@ -777,6 +786,8 @@ static int padic_digits(const mpz_t P, Shape sh) {
 // fthe_padic_m37s (Pt at ctx word kPadicPtWord, above mu's limbs; the tile image of the shifted operand,
 // padic_tiles::build(P, 128, kQShift)); FTHE_NO_M37S=1 keeps fthe_padic_m37t (the same body on the unshifted
 // operand and image), FTHE_NO_M37T=1 keeps fthe_padic_m37 and so switches off both (bit-identical results).
+// The default for the same P is fthe_padic_m37l (product 1 fed the limbs as they lie; the 24 KB image of
+// padic_tiles::build_limb); FTHE_NO_M37L=1 keeps fthe_padic_m37s, and the older switches switch it off too.
 static int upload_padic(DevMod &d, const mpz_t P, int K) {
     Mpz P2; mpz_mul(P2, P, P);
     d.m.init(P2, Shape{2 * K, 28, 1});
@@ -784,8 +795,15 @@ static int upload_padic(DevMod &d, const mpz_t P, int K) {
     std::vector<uint8_t> tiles;
     const bool top_ok = mpz_sizeinbase(P, 2) <= (size_t)kPadicTopBits && !getenv("FTHE_NO_M37T");
     const bool shifted = top_ok && !getenv("FTHE_NO_M37S");
-    if (K == kPadicK && !getenv("FTHE_NO_PADIC_MFMA"))
-        tiles = padic_tiles::build(P, padic_tiles::kS1Lo, shifted ? padic_tiles::kQShift : 0);
+    static_assert(padic_tiles::kLimbMaxBits == kPadicTopBits, "fthe_padic_m37l admits the four-tile body's P");
+    bool limb = shifted && !getenv("FTHE_NO_M37L");
+    if (K == kPadicK && !getenv("FTHE_NO_PADIC_MFMA")) {
+        if (limb) tiles = padic_tiles::build_limb(P);
+        if (tiles.empty()) {
+            limb = false;
+            tiles = padic_tiles::build(P, padic_tiles::kS1Lo, shifted ? padic_tiles::kQShift : 0);
+        }
+    }
     std::vector<uint32_t> w(tiles.empty() ? (size_t)2 * K + 1 + pad : 128 + tiles.size() / 4, 0u), l = to_limbs(P, K, 28);
     if (!tiles.empty()) std::memcpy(w.data() + 128, tiles.data(), tiles.size());
     for (int j = 0; j < K; j++) w[j] = (uint32_t)(-(int32_t)l[j]);
@@ -800,7 +818,7 @@ static int upload_padic(DevMod &d, const mpz_t P, int K) {
     if (hipMalloc(&d.d_ctx, w.size() * 4) != hipSuccess) return FTHE_ERR_NOMEM;
     HIPOK(hipMemcpy(d.d_ctx, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     d.kernel_S = 1000 + K;
-    d.kernel_S_mfma = tiles.empty() ? 0 : shifted ? kPadicMfmaSS : top_ok ? kPadicMfmaTS : kPadicMfmaS;
+    d.kernel_S_mfma = tiles.empty() ? 0 : limb ? kPadicMfmaLS : shifted ? kPadicMfmaSS : top_ok ? kPadicMfmaTS : kPadicMfmaS;
     return FTHE_OK;
 }
 // Algorithmic 32-bit MACs of a P-adic program (SURVEY 8(d) units, the executed algorithm): s = words

@@ -38,6 +38,8 @@ TOPEST_MAX_BITS bits), whose product 2 in the reductions of SQR / MUL runs four 
 1015 from product 1's fraction (see gen_padic_mfma's docstring), its ctx also holding Pt = P >> 1000 at byte PT_OFF;
 and fthe_padic_m37s (top_est=True, q1_shift=8), the same with product 1's operand fed 8 bytes later, which empties
 the four tiles with m - k = 1: 15 product-1 tiles, and the image of padic_tiles::build(P, 128, 8).
+A fourth, fthe_padic_m37l (top_est=True, limb_op=True), feeds product 1 the radix-2^28 limbs of q1 as they lie -- no
+repack into base-256 dwords, the tilted band in 15 tiles of their own: the 24 KB image of padic_tiles::build_limb(P).
 """
 import os
 import sys
@@ -101,13 +103,23 @@ S1_TOP = 272                    # q1 mu has no column above 271
 # 2^32 from bit QBIT - 8, in place of 28-bit limbs repacked by orpack; noq3dw keeps the limb fold
 Q3DW = "noq3dw" not in AB and not LDSX
 QBIT = 28 * 38                  # q3 = floor(N / 2^1064)
+# clampbr: Barrett 1's sign-keyed clamp (37 v_bitop3) is skipped by a wave-uniform branch when no lane's numerator
+# went negative (q1 = 0, or a tiny q1 at P near 2^1030); the mask itself is still formed (the four-tile body's h reads
+# it).  On in fthe_padic_m37l (noclampbr: off), off in the older bodies (clampbr: on); DESIGN 15 has the measurement
+CLAMPBR_ON, CLAMPBR_OFF = "clampbr" in AB.split(','), "noclampbr" in AB.split(',')
 TILE_D1 = (-3, -2, -1, 0, 1)    # product-1 Toeplitz tiles (k <= 3) by m - k; then k = 4 for m = 0..4
 TILE_D2 = (0, 1, 2, 3)          # product-2: k = 0 for m = 0..4 (tiles 10..14), then Toeplitz (k >= 1) by m - k
 
 
-def tile_index(prod, m, k, q1_shift=0):
+def tile_index(prod, m, k, q1_shift=0, limb_op=False):
     """q1_shift (fthe_padic_m37s): no product-1 tile with m - k = 1; tile (0, 0), whose first q1_shift columns are
-    the operand's pad, takes that slot (it is the only one formed with k = 0)"""
+    the operand's pad, takes that slot (it is the only one formed with k = 0).
+    limb_op (fthe_padic_m37l): the 15 product-1 tiles (k >= m) each have a slot, m-major; product 2's nine follow"""
+    if limb_op:
+        if prod == 1:
+            assert k >= m
+            return sum(5 - x for x in range(m)) + k - m
+        return 15 + m if k == 0 else 20 + TILE_D2.index(m - k)
     if prod == 1:
         if q1_shift and k == 0:
             assert m == 0
@@ -125,10 +137,18 @@ TOPEST_C = 128 << 8             # the window constant c = 128 units of 2^1008, i
 
 
 Q1_SHIFT = 8                    # fthe_padic_m37s: q1's byte i is fed at K index i + Q1_SHIFT
+LIMB_PAD = 1                    # fthe_padic_m37l: pad dwords in front of the 38 limbs of product 1's operand
+TILE_BYTES_L = 24 * 1024        # its image: 15 product-1 tiles and product 2's nine
 
 
-def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
-    """q1_shift = 8 (with top_est: fthe_padic_m37s): product 1's operand starts two dwords later -- q1 in D[2..35],
+def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op: bool = False) -> str:
+    """limb_op (with top_est: fthe_padic_m37l): product 1 reads its B operands straight from the limbs
+    T[36..73] (V[36..73] in the second reduction) behind LIMB_PAD pad dwords -- K index 4 (t + LIMB_PAD) + j is byte j
+    of q1's limb t, fed as b ^ 0x80 for j < 3 and as it is for j = 3; the constant digit rides in byte 3 of limb 37
+    (always zero: T < 2^2068) -- so no orpack and no copy precede product 1; the A image (tools/padic_mfma_model.py
+    MfmaKey(P, limb_op=True)) absorbs the layout: 15 product-1 tiles of their own, 24 KB.  The first reduction's q3
+    limbs land in XB (D[2..38]) and are packed in place for product 2; the second reduction's dwords in D[0..31].
+    q1_shift = 8 (with top_est: fthe_padic_m37s): product 1's operand starts two dwords later -- q1 in D[2..35],
     the constant dword (digits 1 and 16 c, K indices 144 and 145) in D[36] -- so that A1[s][i] = mu'[s - i + 8] and
     the sub-diagonal tiles (m - k = 1: s - i + 8 >= 137, above mu's last digit 133) are zero and are not formed: 15
     tiles instead of 19, every column sum unchanged.  The A columns of K indices 0..7 and 146..159 are
@@ -145,6 +165,10 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     K, B = 37, 28
     MASK = (1 << B) - 1
     assert q1_shift in (0, Q1_SHIFT) and not (q1_shift and (LDSX or S1_LO != 128))
+    assert not limb_op or (top_est and not q1_shift and not (LDSX or SPILL or PP) and S1_LO == 128 and PREXOR and Q3DW)
+    CLAMPBR = CLAMPBR_ON or (limb_op and not CLAMPBR_OFF)
+    tile_bytes = TILE_BYTES_L if limb_op else TILE_BYTES
+    lds_bytes = LDS_BYTES - TILE_BYTES + tile_bytes
     QD = q1_shift // 4                           # the operand's first dword
     # ---- VGPR plan ---------------------------------------------------------
     V_TID, V_GOFF = 0, 1
@@ -166,6 +190,15 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     PATV = (249, 250)                            # PREXOR: byte-flip patterns of even / odd limbs
     assert not (SPILL and PREXOR)
     NVGPR = 250 if SPILL else 251 if PREXOR else 249
+    if limb_op:
+        # T[36..73] and V[36..73] are product 1's operand blocks: each sits between two pad registers (v136 / v175,
+        # v212 / v251) that the lane exchange may swap freely, 40 consecutive registers from an even one
+        VV = TT + 2 * K + 2
+        V_LDS = VV + 2 * K + 2
+        PATV = (V_LDS + 1, V_LDS + 2)
+        NVGPR = V_LDS + 3
+        assert NVGPR <= 256
+    L36 = "v14"                                  # limb_op: the unflipped copy of limb 36 (the remainder's init)
     V_XW, V_XR = NVGPR, NVGPR + 1                # LDSX: this wave's exchange area + lane * 16, and ^ 512
     if LDSX:
         NVGPR += 2
@@ -178,6 +211,20 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     X1 = [f"v{XB + i}" for i in range(K)]
     T = [f"v{TT + i}" for i in range(2 * K)]
     V = [f"v{VV + i}" for i in range(2 * K)]
+    if limb_op:
+        lay = lambda base: [f"v{base + i + (i >= K - 1)}" for i in range(2 * K)]
+        blk = lambda base: [f"v{base + K - 1 + i}" for i in range(40)]
+        T, V = lay(TT), lay(VV)
+        OPB = {id(T): blk(TT), id(V): blk(VV)}   # pad, limbs 36..73, pad
+        assert OPB[id(T)][LIMB_PAD:LIMB_PAD + K + 1] == T[K - 1:] and OPB[id(V)][LIMB_PAD:LIMB_PAD + K + 1] == V[K - 1:]
+
+    def pxu(c):
+        """flip pattern that limb c >= K of a product leaves its column tail with (PREXOR): as a byte of q1 packed
+        from limb K - 1 on, or (limb_op) bytes 0..2 of the limb itself, the top limb also taking the constant digit 1
+        into its byte 3 (a literal: its tail is a v_xor_b32_e32)"""
+        if limb_op:
+            return "0x1808080" if c == 2 * K - 1 else f"v{PATV[0]}"
+        return pat(c - (K - 1))
     D = [f"v{XB + i}" for i in range(40)]
     # ---- SGPR plan ---------------------------------------------------------
     # s[0:1] kernarg, s2 wg id, s[2:3] call target, s[4:5] slots, s[6:7] prog, s[8:9] ctx, s10 limb
@@ -327,7 +374,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
                         terms.append((a2[i], b2[j]))
             cols.append({'terms': terms, 'out': outs[c], 'last': c == n_out - 1})
             if PREXOR and c >= K:                      # the upper half only feeds Barrett's q1 bytes
-                cols[-1]['px'] = pat(c - (K - 1))
+                cols[-1]['px'] = pxu(c)
         return cols
 
     def move(dst, src):
@@ -393,6 +440,8 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     # the second reduction's product-2 operand block (Q3DW): dwords 0..35 in V[38..73] (its q1 limbs, dead once
     # packed), 36..39 in the product phase's accumulators v16..v19
     D2 = [f"v{VV + 38 + i}" for i in range(36)] + [f"v{16 + i}" for i in range(4)]
+    if limb_op:                                 # V[36..73] is product 1's operand: the dwords go to XB
+        D2 = D
     OPND = [D]                                  # the block the MFMAs read their B operands from
 
     def swap_operands(Dl=D, nk=5):
@@ -423,7 +472,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
 
     def rd(prod, m, k, n):
         b_ = VA[n % 3]
-        e(f'  ds_read_b128 v[{b_}:{b_ + 3}], v{V_LDS} offset:{1024 * tile_index(prod, m, k, q1_shift)}')
+        e(f'  ds_read_b128 v[{b_}:{b_ + 3}], v{V_LDS} offset:{1024 * tile_index(prod, m, k, q1_shift, limb_op)}')
 
     def prefetch(prod, m, ks):
         """the first two A-tile reads of M-tile m (issued while the lane still has VALU work)"""
@@ -713,13 +762,15 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             ch.column(s_, r_)
             i += 1
 
-    P1_TILES = [(1, m, [k for k in range(5) if m - k <= (0 if q1_shift else 1)]) for m in range(5)]
+    P1_TILES = [(1, m, [k for k in range(5) if m - k <= (0 if q1_shift or limb_op else 1)]) for m in range(5)]
     P2_TILES = [(2, m, [k for k in range(5) if m >= k]) for m in range(5)]
     assert P1_TILES[0][2][0] != 4 and P2_TILES[0][2][0] != 4      # LDSX: see swap_operands
 
     V_FRAC = XA + 37                            # top_est: f32, the 32 bits of N below QBIT (v57)
     assert V_FRAC not in range(G0, G0 + 32) and V_FRAC not in range(XA + 32, XA + 37) and \
         V_FRAC not in (XA + 38, XA + 39) and V_FRAC < XB and V_FRAC >= CARRY + 2 and V_FRAC not in VA
+
+    nclamp = [0]
 
     def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None, dw=None, t4=False):
         """product 1: q3 = Barrett's quotient of T (Tl: 2K limbs, Tl[K-1] < 2^29 allowed) -> q3out (K regs,
@@ -734,14 +785,25 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             pre_in = PREXOR
         if not prefetched:
             prefetch(*P1_TILES[0])
-        orpack(Tl[K - 1:2 * K], 0, 34, [0x80808080] * 34, norm0=True, pre=range(1, K + 1) if pre_in else (), d0=QD)
-        DC = D[34 + QD]
-        e(f'  v_bfe_u32 {DC}, {Tl[K - 1]}, 28, 1')                  # c = bit 28 of q1[0] -> digit 16 c at byte 137
-        e(f'  v_lshl_or_b32 {DC}, {DC}, 12, 1')                     # and the constant digit 1 at byte 136
-        if not q1_shift:                                            # q1_shift: the pads meet zero A columns
-            for w in range(35, 40):
-                e(f'  v_mov_b32_e32 {D[w]}, 0')
-        swap_operands()
+        if limb_op:
+            # the limbs are the operand: limb 36 (not pre-flipped: the remainder's init, copied) is flipped in
+            # place; its byte 3 (bit 28 included) and the others' are valid i8 as they are
+            e(f'  v_mov_b32_e32 {L36}, {Tl[K - 1]}')
+            e(f'  v_xor_b32_e32 {Tl[K - 1]}, v{PATV[0]}, {Tl[K - 1]}')
+            if not pre_in:                                          # LOADP: plain limbs
+                for t in range(K, 2 * K):
+                    e(f'  v_xor_b32_e32 {Tl[t]}, {pxu(t)}, {Tl[t]}')
+            swap_operands(OPB[id(Tl)])
+            OPND[0] = OPB[id(Tl)]
+        else:
+            orpack(Tl[K - 1:2 * K], 0, 34, [0x80808080] * 34, norm0=True, pre=range(1, K + 1) if pre_in else (), d0=QD)
+            DC = D[34 + QD]
+            e(f'  v_bfe_u32 {DC}, {Tl[K - 1]}, 28, 1')                  # c = bit 28 of q1[0] -> digit 16 c at byte 137
+            e(f'  v_lshl_or_b32 {DC}, {DC}, 12, 1')                     # and the constant digit 1 at byte 136
+            if not q1_shift:                                            # q1_shift: the pads meet zero A columns
+                for w in range(35, 40):
+                    e(f'  v_mov_b32_e32 {D[w]}, 0')
+            swap_operands()
         if dw is None:
             # chunk -1 is bits 1036..1063 of N: f32 = its 28 bits over four zeros
             tap = {-1: lambda lo: [f'  v_lshlrev_b32_e32 v{V_FRAC}, 4, {lo}']} if t4 else None
@@ -772,17 +834,26 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             fold_columns(ch, tile_cols(1, m, lambda rho: S1_LO + 32 * m + rho, creg))
         run_tiles(P1_TILES, consume, P2_TILES[0], dbuf, setb=setb)
         ch.finish()
+        OPND[0] = D
         P1_TOP[0] = S1_TOP
         if clamp:                                  # final carry = 0, or -1 when the numerator < 0 (q3 = -1 -> 0)
             e(f'  v_not_b32_e32 v{XA + 36}, v{XA + 38}')
+            if CLAMPBR:                            # no lane of the wave went negative (the usual case): mask all ones
+                nclamp[0] += 1
+                e(f'  v_cmp_ne_u32_e32 vcc, 0, v{XA + 38}')
+                e('  s_nop 4')                     # VALU vcc -> vccz read
+                e(f'  s_cbranch_vccz .Lnoclamp{nclamp[0]}')
             for t, r in enumerate(q3out):
                 if PREXOR:                         # ((r ^ pat) & m) ^ pat
                     e(f'  v_bitop3_b32 {r}, {r}, v{XA + 36}, {pat(t)} bitop3:0xe2')
                 else:
                     e(f'  v_and_b32_e32 {r}, {r}, v{XA + 36}')
+            if CLAMPBR:
+                e(f'.Lnoclamp{nclamp[0]}:')
         return q3out
 
-    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None, dw=None, t4=False, clamped=False):
+    def mfma_remainder(Tl, q3, rout, nxt_p1, dbuf=False, after_pack=None, dw=None, t4=False, clamped=False,
+                       inits=None):
         """product 2: r = (T - q3 P) mod b^K -> rout (may be Tl[:K]); the product-2 tile-0 reads are already
         in flight; nxt_p1: prefetch product 1's first tiles at the end (the next Barrett); after_pack: the
         caller's last use of the q3 limbs (dbuf may then take their registers); dw: the operand block whose
@@ -792,6 +863,14 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
         docstring); clamped: mfma_barrett forced a negative quotient to 0 (r = T < 2^1016): h = 0 under its mask"""
         Dl = D if dw is None else dw
         nk = 4 if t4 else 5
+        if limb_op and dw is None:
+            # q3's limbs lie in D[2..38] and are packed in place: dword w reads limbs (32 w - 8) div 28 >= w - 1 and
+            # the next, so D[w] holds a limb no later dword reads; the caller's use of the limbs comes first
+            if after_pack:
+                after_pack()
+                after_pack = None
+            for w in range(33):
+                assert D[w] not in q3[max(0, (32 * w - 8) // B):]
         if dw is None:
             orpack(q3, 8, 32 if t4 else 33, [0x80808000] + [0x80808080] * 32, lead_one=True,
                    pre=range(K) if PREXOR else ())
@@ -804,7 +883,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
         swap_operands(Dl, nk)
         OPND[0] = Dl
         # matrix column s holds column s - 1 of q3 P (bits 8 s - 8): P'[s - i] is a plain Toeplitz band
-        ch = Chunks(8, 0, K - 1, rout, neg=True, inits=Tl[:K], nocarry_last=True)
+        ch = Chunks(8, 0, K - 1, rout, neg=True, inits=inits or Tl[:K], nocarry_last=True)
 
         def consume(m, creg):
             fold_columns(ch, tile_cols(2, m, lambda rho: 32 * m + rho, creg))
@@ -897,11 +976,11 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
         e('  v_lshlrev_b32_e32 v10, 4, v10')
     else:
         e(f'  v_lshlrev_b32_e32 v10, 4, v{V_TID}')
-    for it in range(TILE_BYTES // 4096):
+    for it in range(tile_bytes // 4096):
         e(f'  global_load_dwordx4 v[2:5], v10, s[8:9] offset:{TILE_OFF}')
         e('  s_waitcnt vmcnt(0)')
         e('  ds_write_b128 v10, v[2:5]')
-        if it != TILE_BYTES // 4096 - 1:
+        if it != tile_bytes // 4096 - 1:
             e('  v_add_u32_e32 v10, 0x1000, v10')
     e(f'  v_and_b32_e32 v{V_LDS}, 63, v{V_TID}')
     e(f'  v_lshlrev_b32_e32 v{V_LDS}, 4, v{V_LDS}')
@@ -1040,14 +1119,14 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             terms = [(S0[i], S1[k - i]) for i in range(19) if 0 <= k - i < 19]
             col = {'terms': terms, 'out': V[k + 19], 'addend': f'v[{tl[1:]}:{int(tl[1:]) + 1}]', 'pre': pre}
             if PREXOR and k + 19 >= K:
-                col['px'] = pat(k + 19 - (K - 1))
+                col['px'] = pxu(k + 19)
             cols.append(col)
         columns(cols, carry_in=True)
         # 4. ripple: v = (mask ^ P2c_19) + carry - 3, then limb / carry through V[73] (v2 value, v3 carry)
         e(f'  v_xad_u32 v2, {V[57]}, {SMASK}, v{CARRY}')
         rip = ['  v_add_u32_e32 v2, -3, v2']
         for j in range(57, 2 * K):
-            px = pat(j - (K - 1)) if PREXOR else None
+            px = pxu(j) if PREXOR else None
             if j == 2 * K - 1:
                 rip.append(f'  v_xor_b32_e32 {V[j]}, {px}, v2' if px else f'  v_mov_b32_e32 {V[j]}, v2')
                 break
@@ -1072,7 +1151,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             terms = [(X0[i], X1[c - i]) for i in range(K) if 0 <= c - i < K]
             cols.append({'terms': terms, 'dbl': True, 'out': V[c], 'last': c == 2 * K - 1})
             if PREXOR and c >= K:
-                cols[-1]['px'] = pat(c - (K - 1))
+                cols[-1]['px'] = pxu(c)
         columns(cols)
     cols = []
     for c in range(2 * K):
@@ -1080,7 +1159,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
         sq = X0[c // 2] if c % 2 == 0 and c // 2 < K else None
         col = {'terms': terms, 'out': T[c], 'last': c == 2 * K - 1}
         if PREXOR and c >= K:
-            col['px'] = pat(c - (K - 1))
+            col['px'] = pxu(c)
         if terms:
             col['dbl'] = True
             if sq:
@@ -1112,11 +1191,21 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     e('.Lloadp:')
     load_limbs(T)
     phase()
-    q3 = mfma_barrett(T, T[K:], clamp=True, pre_in=False)
-    mfma_remainder(T, q3, T[:K], nxt_p1=False)
+    Q = D[2:2 + K]                               # limb_op: the first reduction's q3 limbs
+    RINIT = (lambda Tl: Tl[:K - 1] + [L36]) if limb_op else (lambda Tl: None)
+    if limb_op:
+        q3 = mfma_barrett(T, Q, clamp=True, pre_in=False)
+        for i in range(K):                       # x1 waits, unflipped, where product 1's operand has died
+            e(f'  v_xor_b32_e32 {T[K + i]}, {pat(i)}, {Q[i]}')
+        mfma_remainder(T, q3, T[:K], nxt_p1=False, inits=RINIT(T))
+    else:
+        q3 = mfma_barrett(T, T[K:], clamp=True, pre_in=False)
+        mfma_remainder(T, q3, T[:K], nxt_p1=False)
     phase()
     move(X0, T[:K])
-    if PREXOR:
+    if limb_op:
+        move(X1, T[K:2 * K])
+    elif PREXOR:
         for i in range(K):
             e(f'  v_xor_b32_e32 {X1[i]}, {pat(i)}, {T[K + i]}')
     else:
@@ -1197,7 +1286,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
         for j in range(9):
             e(f'  ds_write_b128 v{V_SPILL}, v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}] offset:{1024 * j}')
         e(f'  ds_write_b32 v{V_SPILL}, {V[K]} offset:{9 * 1024}')
-    q3 = mfma_barrett(T, T[K:], clamp=True, dbuf=spill, setb=(GV0, GV1), t4=top_est)    # u1 -> T[K..2K-1]
+    q3 = mfma_barrett(T, Q if limb_op else T[K:], clamp=True, dbuf=spill, setb=(GV0, GV1), t4=top_est)    # u1 -> T[K..2K-1]
 
     def add_u1():
         for i in range(K):
@@ -1209,10 +1298,11 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
             for j in range(9):
                 e(f'  ds_read_b128 v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}], v{V_SPILL} offset:{1024 * j}')
             e(f'  ds_read_b32 {V[K]}, v{V_SPILL} offset:{9 * 1024}')
-    mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True)    # u0 -> T[0..K-1]
+    mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True,
+                   inits=RINIT(T))               # u0 -> T[0..K-1]
     if Q3DW:
         mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2, t4=top_est)    # T[K..] is free
-        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2, t4=top_est)
+        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2, t4=top_est, inits=RINIT(V))
     else:
         q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf, t4=top_est)
         mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf, t4=top_est)
@@ -1225,7 +1315,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0) -> str:
     e(f'.Lfunc_end_{name}:')
     e(f'  .size {name}, .Lfunc_end_{name}-{name}')
     e('')
-    o.extend(_descriptor(name, LDS_BYTES, NVGPR, 98 if DYN else 90 if STAMP else NSGPR,
+    o.extend(_descriptor(name, lds_bytes, NVGPR, 98 if DYN else 90 if STAMP else NSGPR,
                          max_wg=512 if PP else 256).splitlines())
     return "\n".join(o) + "\n"
 
@@ -1236,7 +1326,8 @@ if __name__ == "__main__":
     ap.add_argument('--name', default='fthe_padic_m37')
     ap.add_argument('--top-est', action='store_true', help='the four-tile body (fthe_padic_m37t)')
     ap.add_argument('--q1-shift', type=int, default=0, help='8 with --top-est: the shifted operand (fthe_padic_m37s)')
+    ap.add_argument('--limb-op', action='store_true', help='with --top-est: the limb-fed product 1 (fthe_padic_m37l)')
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:
-        f.write(gen_padic_mfma(a.name, top_est=a.top_est, q1_shift=a.q1_shift))
+        f.write(gen_padic_mfma(a.name, top_est=a.top_est, q1_shift=a.q1_shift, limb_op=a.limb_op))

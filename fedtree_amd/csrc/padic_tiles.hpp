@@ -19,6 +19,7 @@
 // v_mfma_i32_32x32x32_i8 A map).  Order: product 1 Toeplitz m - k = -3..1 (k <= 3), product 1 k = 4 for
 // m = 0..4, product 2 k = 0 for m = 0..4, product 2 Toeplitz m - k = 0..3 (k >= 1).  19 tiles, padded to
 // 20 KB (the kernel's LDS fill).  build(P, 128, 8) is the image of fthe_padic_m37s (see build).
+// build_limb(P) is the image of fthe_padic_m37l, whose product 1 is fed q1's radix-2^28 limbs as they lie (see there).
 #pragma once
 #include <gmp.h>
 #include <cstdint>
@@ -27,6 +28,10 @@
 namespace padic_tiles {
 
 constexpr int kTiles = 19, kImageBytes = 20 * 1024, kS1Lo = 128, kNq1 = 136, kConst1 = 136, kNq3 = 132, kQShift = 8;
+// fthe_padic_m37l: 15 product-1 tiles and product 2's nine; kLimbPad pad dwords in front of the 38 limbs; the
+// constant digit in byte 3 of limb 37; P of at most kLimbMaxBits bits (the four-tile body's range)
+constexpr int kLimbTiles = 24, kLimbImageBytes = 24 * 1024, kLimbPad = 1, kLimbConst = 4 * (kLimbPad + 37) + 3,
+              kLimbMaxBits = 1027;
 
 // n balanced base-256 digits of x >= 0; false if they do not hold x
 inline bool balanced(const mpz_t x, int n, std::vector<int> &d) {
@@ -123,6 +128,71 @@ inline std::vector<uint8_t> build(const mpz_t P, int s1lo = kS1Lo, int qshift = 
     for (int m = 0; m < 5; m++) tile(2, 0, m, 0);
     for (int d = 0; d <= 3; d++) tile(2, 0, d + 1, 1);
     img.resize(kImageBytes, 0);
+    return img;
+}
+
+// the image of fthe_padic_m37l (tools/padic_mfma_model.py MfmaKey(P, limb_op=True).tile_image()): product 1's digit
+// index 4 (t + kLimbPad) + j is byte j of q1's limb t, at bit e = 28 t + 8 j of q1, so A1[s][.] is the balanced digit
+// s - e / 8 of mu 2^(e mod 8) -- of mu for even t, of 16 mu for odd t; bytes 0..2 are fed as b - 128 and byte 3 as it
+// is, so g1 = (128 mu sum_{t<38, j<3} 2^(28 t + 8 j) - 2^1046) >> 1024, in the column of kLimbConst (byte 3 of limb
+// 37, which is always zero).  The band is tilted (7 bits per digit index, 8 per column), so each of the 15 tiles
+// with k >= m has a slot of its own, m-major; every other product-1 tile is zero.  Product 2's tiles follow as in
+// build.  Empty on failure or for P outside 1009..kLimbMaxBits bits.
+inline std::vector<uint8_t> build_limb(const mpz_t P) {
+    std::vector<uint8_t> img;
+    if (mpz_sizeinbase(P, 2) < 1009 || mpz_sizeinbase(P, 2) > (size_t)kLimbMaxBits) return img;
+    mpz_t mu, c, b;
+    mpz_inits(mu, c, b, nullptr);
+    mpz_set_ui(mu, 1);
+    mpz_mul_2exp(mu, mu, 56 * 37);
+    mpz_fdiv_q(mu, mu, P);
+    std::vector<int> mud[2], pd, g1, g2;
+    bool ok = balanced(mu, 136, mud[0]) && balanced(P, 130, pd);
+    mpz_mul_2exp(c, mu, 4);
+    ok = ok && balanced(c, 136, mud[1]);
+    mpz_set_ui(c, 0);
+    for (int t = 0; t < 38; t++)
+        for (int j = 0; j < 3; j++) mpz_setbit(c, 28 * t + 8 * j);
+    mpz_mul(c, c, mu);
+    mpz_mul_ui(c, c, 128);
+    mpz_set_ui(b, 1);
+    mpz_mul_2exp(b, b, 8 * kS1Lo + 22);
+    mpz_sub(c, c, b);
+    mpz_fdiv_q_2exp(c, c, 8 * kS1Lo);
+    ok = ok && balanced(c, 160, g1);
+    offset_sum(c, P, kNq3);
+    mpz_fdiv_r_2exp(c, c, 1040);
+    ok = ok && balanced(c, 131, g2);
+    mpz_clears(mu, c, b, nullptr);
+    if (!ok) return img;
+    g2.resize(130);
+    auto a1 = [&](int s, int i) -> int {
+        const int t = i / 4 - kLimbPad, j = i % 4;
+        if (t < 0 || t >= 38) return 0;
+        if (i == kLimbConst) return (s >= kS1Lo && s < kS1Lo + 160) ? g1[s - kS1Lo] : 0;
+        const int e = 28 * t + 8 * j, d = s - e / 8;
+        const std::vector<int> &m = mud[(e % 8) / 4];
+        return (d >= 0 && d < (int)m.size()) ? m[d] : 0;
+    };
+    auto a2 = [&](int s, int i) -> int {
+        if (i == 0) return (s >= 1 && s <= (int)g2.size()) ? g2[s - 1] : 0;
+        int j = s - i;
+        return (j >= 0 && j < (int)pd.size()) ? pd[j] : 0;
+    };
+    img.reserve(kLimbImageBytes);
+    auto tile = [&](int prod, int s_base, int m, int k) {
+        for (int l = 0; l < 64; l++) {
+            const int r = l & 31, h = l >> 5;
+            for (int j = 0; j < 16; j++) {
+                const int s = s_base + 32 * m + r, i = 32 * k + 16 * h + j;
+                img.push_back((uint8_t)((prod == 1 ? a1(s, i) : a2(s, i)) & 255));
+            }
+        }
+    };
+    for (int m = 0; m < 5; m++)
+        for (int k = m; k < 5; k++) tile(1, kS1Lo, m, k);
+    for (int m = 0; m < 5; m++) tile(2, 0, m, 0);
+    for (int d = 0; d <= 3; d++) tile(2, 0, d + 1, 1);
     return img;
 }
 

@@ -6,6 +6,8 @@
 #   bash tools/m37_ab.sh TAG base t     runs m37 and m37t round-robin in one series.
 # A variant named s or s_* holds fthe_padic_m37s (--top-est --q1-shift 8) and reads the shifted tile image:
 #   bash tools/m37_ab.sh TAG t s
+# A variant named l or l_* holds fthe_padic_m37l (--top-est --limb-op) and reads the limb-fed tile image:
+#   bash tools/m37_ab.sh TAG s l
 T=${1:?tag}; shift
 N=${M37_LANES:-393216}
 mkdir -p gpurun_out
@@ -18,6 +20,7 @@ for r in 1 2 3; do
     # the harness looks up M37_KERNEL, when set, in place of the kernel named on its command line
     unset M37_KERNEL; [[ $v == t || $v == t_* ]] && export M37_KERNEL=fthe_padic_m37t
     export M37_QSHIFT=0; [[ $v == s || $v == s_* ]] && export M37_KERNEL=fthe_padic_m37s M37_QSHIFT=8
+    export M37_LIMB=0; [[ $v == l || $v == l_* ]] && export M37_KERNEL=fthe_padic_m37l M37_LIMB=1
     M37_BLOCK=$blk timeout -k 10 120 tools/bin/test_padic tools/bin/m37_$v.hsaco $N 0 fthe_padic_m37 > gpurun_out/${T}_one.json
     rc=$?
     # timing-only variants (nomfma, noswap, nonop: wrong results by design) may report bad lanes (rc 1)

@@ -43,6 +43,14 @@ order of the LDS image that the kernel reads (tile_image), which the host code m
 fthe_padic_m37s feeds product 1's operand 8 digit positions later (MfmaKey(P, q_shift=8)): the same column sums
 from 15 tiles instead of 19 (see MfmaKey).
 
+fthe_padic_m37l feeds product 1 the 38 radix-2^28 limbs of q1 as they lie (MfmaKey(P, limb_op=True)): other
+column sums, the same Pi = q1 mu and the same window.  Operand digit 4 (t + 1) + j is byte j of limb t, at bit
+e = 28 t + 8 j of q1, so its A column holds the balanced digits of mu 2^(e mod 8) from column e div 8 on.  Bytes 0..2
+are fed as b ^ 0x80, byte 3 (at most 31) as it is, so the offset's correction is c1 = 128 mu sum_{t<38, j<3} 2^(28 t +
+8 j); the constant digit rides in byte 3 of limb 37, which is zero for T < 2^2068.  A column sum has at most 154
+terms of at most 2^14: |c_s| < 2^21.3, the dropped columns hold |L| < 2^(1024 + 13.4), and Pi - 2^1047 < N < Pi as
+before; the quotient may differ from the byte-fed form's by one (then the remainder by P).
+
 Run:  python tools/padic_mfma_model.py [seed] [trials]
 """
 import os
@@ -91,6 +99,14 @@ def balanced(x, n):
 
 
 Q1_SHIFT = 8                     # fthe_padic_m37s: q1's byte i is fed at digit index i + 8 (two dwords later)
+# fthe_padic_m37l (MfmaKey(P, limb_op=True)): product 1 is fed q1's 38 radix-2^28 limbs as they lie, one
+# per operand dword, behind LIMB_PAD pad dwords: digit index 4 (t + LIMB_PAD) + j is byte j of limb t, at bit
+# 28 t + 8 j of q1.  Bytes 0..2 are fed as b ^ 0x80, byte 3 (0..15; 0..31 for limb 0, which may hold a bit 28) as it
+# is; byte 3 of limb 37 is always zero (T < 2^2068) and carries the constant digit 1.
+LIMB_PAD = 1
+LIMB_CONST = 4 * (LIMB_PAD + 37) + 3
+LIMB_T_BITS = 2068               # the reduced value is below 2^LIMB_T_BITS: limb 73 < 2^24
+LIMB_ENTRIES = 154               # a column sum has at most this many non-zero terms, each at most 2^14
 
 
 class MfmaKey(pm.PadicKey):
@@ -99,11 +115,13 @@ class MfmaKey(pm.PadicKey):
     with m - k = 1 hold only mu' digits from index 137 on: zero, since mu < 2^1064 ends at digit 133.  Any shift
     (a multiple of 4 up to 20) is modelled, so that the tests can show that 4 does not empty those tiles."""
 
-    def __init__(self, P, s1_lo=S1_LO, q_shift=0):
+    def __init__(self, P, s1_lo=S1_LO, q_shift=0, limb_op=False):
         super().__init__(P, K)
         assert s1_lo in (112, 128)                          # 112: the window and bias of rounds 2-6
         assert q_shift == 0 or (s1_lo == 128 and q_shift % 4 == 0 and 0 < q_shift <= 160 - CONST1 - 2)
+        assert not limb_op or (s1_lo == 128 and q_shift == 0)
         self.q_shift = q_shift
+        self.limb_op = limb_op
         self.s1_lo, self.bias_bits = s1_lo, 8 * s1_lo + 22
         mu = pm.value(self.mu)
         self.mu_d = balanced(mu, 135)                       # mu < 2^1063: 134 digits + a carry digit
@@ -113,9 +131,28 @@ class MfmaKey(pm.PadicKey):
         self.g1 = balanced(g1, 160)
         c2 = 128 * P * sum(256 ** i for i in range(NQ3))
         self.g2 = balanced(c2 % (1 << 1040), 131)[:130]     # mod 2^1040 (columns < 130; 256^130 = 0 mod b^K)
+        if limb_op:
+            # the limb-fed operand advances 7 bits per digit index against 8 per column: the A entry of byte j of
+            # limb t (bit e = 28 t + 8 j) is a digit of mu 2^(e mod 8), i.e. of mu (even t) or 16 mu (odd t)
+            self.mu_dl = (balanced(mu, 136), balanced(16 * mu, 136))
+            c1 = 128 * mu * sum(1 << (B * t + 8 * j) for t in range(38) for j in range(3))
+            self.g1 = balanced((c1 - (1 << self.bias_bits)) >> (8 * s1_lo), 160)
+
+    def a1_limb(self, s, i):
+        u, j = divmod(i, 4)
+        t = u - LIMB_PAD
+        if not 0 <= t < 38:
+            return 0                            # the pad dwords
+        if i == LIMB_CONST:
+            return self.g1[s - self.s1_lo] if self.s1_lo <= s < self.s1_lo + 160 else 0
+        a, b = divmod(B * t + 8 * j, 8)
+        d = self.mu_dl[b // 4]
+        return d[s - a] if 0 <= s - a < len(d) else 0
 
     # A[s][i] of the two products (s: output column, i: B digit index)
     def a1(self, s, i):
+        if self.limb_op:
+            return self.a1_limb(s, i)
         i -= self.q_shift                       # the digit index of the unshifted layout; the pad columns are zero
         if i < 0:
             return 0
@@ -139,7 +176,7 @@ class MfmaKey(pm.PadicKey):
 
     def d1_max(self):
         """product 1 forms the tiles with m - k <= d1_max"""
-        return 0 if self.q_shift else 1
+        return 0 if self.q_shift or self.limb_op else 1
 
     def tiles1(self):
         """product 1's tiles as the kernel forms them: {m: [k ...]}"""
@@ -147,6 +184,9 @@ class MfmaKey(pm.PadicKey):
 
     def tile1_slot(self, m, k):
         """the image tile that the kernel reads for product 1's tile (m, k) (gen_padic_mfma.tile_index)"""
+        if self.limb_op:                        # the band is tilted: every tile has a slot of its own, m-major
+            assert k >= m
+            return sum(5 - x for x in range(m)) + k - m
         if k == 4:
             return 5 + m
         if self.q_shift and k == 0:
@@ -186,6 +226,16 @@ class MfmaKey(pm.PadicKey):
                 r, h = l & 31, l >> 5
                 for j in range(16):
                     out.append(fn(s_base + 32 * m + r, 32 * k + 16 * h + j) & 255)
+        if self.limb_op:                        # 15 product-1 tiles in slot order, then product 2's nine: 24 KB
+            for m in range(5):
+                for k in range(m, 5):
+                    assert self.tile1_slot(m, k) * 1024 == len(out)
+                    tile(self.a1, self.s1_lo, m, k)
+            for m in range(5):
+                tile(self.a2, 0, m, 0)
+            for d in TILE_D2:
+                tile(self.a2, 0, d + 1, 1)
+            return bytes(out)
         if self.q_shift:                        # Toeplitz d = -3..0 (k = 3), then tile (0, 0) in the slot of d = 1
             assert self.q_shift == Q1_SHIFT
             for d in TILE_D1[:4]:
@@ -249,15 +299,27 @@ def columns1(key, q1, pad=None):
     assert c in (0, 1)
     qd = key.q_shift // 4
     fill = pad or (lambda: 0)
-    dw = [fill() for _ in range(qd)] + orpack([q1[0] & MASK] + list(q1[1:]), 0, 34) + [1 | (c << 12)]
-    dw += [fill() if qd else 0 for _ in range(40 - len(dw))]
-    dig = digits_of(dw, [0] * qd + [0x80808080] * 34 + [0] * (6 - qd))
-    assert dig[CONST1 + key.q_shift] == 1 and dig[CONST1 + 1 + key.q_shift] == 16 * c
+    if key.limb_op:
+        assert all(0 <= v <= MASK for v in q1[1:]) and q1[37] < (1 << (LIMB_T_BITS - B * 73)), "limb 73's byte 3"
+        dw = [fill() for _ in range(LIMB_PAD)] + list(q1) + [fill() for _ in range(2 - LIMB_PAD)]
+        dig = digits_of(dw, [0] * LIMB_PAD + [0x00808080] * 37 + [0x01808080] + [0] * (2 - LIMB_PAD))
+        assert dig[LIMB_CONST] == 1 and all(0 <= dig[4 * (t + LIMB_PAD) + 3] < (32 if t == 0 else 16) for t in range(37))
+    else:
+        dw = [fill() for _ in range(qd)] + orpack([q1[0] & MASK] + list(q1[1:]), 0, 34) + [1 | (c << 12)]
+        dw += [fill() if qd else 0 for _ in range(40 - len(dw))]
+        dig = digits_of(dw, [0] * qd + [0x80808080] * 34 + [0] * (6 - qd))
+        assert dig[CONST1 + key.q_shift] == 1 and dig[CONST1 + 1 + key.q_shift] == 16 * c
     col = {}
     tiles = key.tiles1()
     for s in range(key.s1_lo, S1_TOP):
         ks = tiles[(s - key.s1_lo) // 32]
         col[s] = s32(sum(key.a1(s, i) * dig[i] for k in ks for i in range(32 * k, 32 * k + 32) if dig[i]))
+    if key.limb_op:
+        # 152 operand bytes and the constant digit, |a b| <= 2^14 each: |c_s| < 2^21.3, so the dropped columns hold
+        # |L| < 2^21.3 256^128 / 255 < 2^(1024 + 13.4) and the pair sums of the fold stay in 32 bits
+        for s in range(key.s1_lo, S1_TOP):
+            assert abs(col[s]) <= LIMB_ENTRIES << 14, "column sum bound"
+            assert abs(col[s] + 256 * col.get(s + 1, 0)) < (1 << 31), "pairing bound"
     Pi = pm.value(q1) * pm.value(key.mu)
     N = sum(v << (8 * s) for s, v in col.items())
     assert Pi - (1 << (key.bias_bits + 1)) < N < Pi and key.bias_bits + 1 <= QBIT, "Pi - 2^1064 < N < Pi"
@@ -558,6 +620,36 @@ def main():
     install()
     print(f"ok: {trials} keys through the four-tile product 2 (fthe_padic_m37t): largest distance "
           f"{SLACK['d_max'] / 256:.2f} of the {TOPEST_C // 256} units asserted (256 between candidates)")
+    # fthe_padic_m37l: the same reductions with product 1 fed the limbs as they lie
+    install_top()
+    SLACK["d_max"] = 0
+    for t in range(trials):
+        bits = rng.choice([1009, 1010, 1023, 1024, 1024, 1026, TOPEST_MAX_BITS])
+        P = rng.getrandbits(bits) | (1 << (bits - 1)) | 1
+        if t == 0:
+            P = (1 << TOPEST_MAX_BITS) - 1
+        key = MfmaKey(P, limb_op=True)
+        assert len(key.tile_image()) == 24 * 1024
+        key.check_skipped_tiles()
+        P2 = P * P
+        top = TOPEST_DIGIT * P - 1
+        for x0v, x1v in ((top, top), (1, 0), (0, 1), (P - 1, P - 1), (2 * P - 1, 2 * P - 1),
+                         (rng.randrange(top), rng.randrange(top))):
+            z0, z1 = pm.sqr(key, pm.limbs(x0v, K), pm.limbs(x1v, K))
+            X = x0v + x1v * P
+            assert (pm.value(z0) + pm.value(z1) * P) % P2 == X * X % P2
+            y0, y1 = pm.mul(key, z0, z1, pm.limbs(x0v, K), pm.limbs(x1v, K))
+            assert (pm.value(y0) + pm.value(y1) * P) % P2 == X ** 3 % P2
+            assert max(pm.value(y0), pm.value(y1)) < P + (1 << 1015)
+        for X in (0, 1, 5, (1 << 1008) - 1, 1 << 1008, 3 * P2 - 1, rng.randrange(P2)):      # LOADP
+            q3, r, cl = barrett(key, pm.limbs(X, 2 * K))
+            assert pm.value(q3) * P + pm.value(r) == X
+        if t < 2:
+            X, ex = rng.randrange(P2), rng.getrandbits(48) | 1
+            assert pm.value(pm.padic_pow(key, X, ex)) % P2 == pow(X, ex, P2)
+    install()
+    print(f"ok: {trials} keys through the limb-fed product 1 (fthe_padic_m37l): largest distance "
+          f"{SLACK['d_max'] / 256:.2f} of the {TOPEST_C // 256} units asserted")
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@
 //        kernel: fthe_padic_k37 (default), fthe_padic_m37 (gen_padic_mfma.py: ctx carries the LDS tile image) or
 //        fthe_padic_m37t (its four-tile body: ctx also carries Pt = P >> 1000 at word 100)
 //        fthe_padic_m37s (the four-tile body on the shifted operand: M37_QSHIFT=8 selects its tile image)
+//        fthe_padic_m37l (the four-tile body on the limb-fed operand: M37_LIMB=1 selects its 24 KB tile image)
 // Checks sampled lanes against GMP's mpz_powm and prints the launch time and products per second.
 #include <hip/hip_runtime.h>
 #include <gmp.h>
@@ -90,7 +91,8 @@ int main(int argc, char **argv) {
     mpz_urandomb(P, rs, 1024); mpz_setbit(P, 1023); mpz_setbit(P, 1022); mpz_setbit(P, 0);
     mpz_mul(P2, P, P);
     mpz_set_ui(t, 1); mpz_mul_2exp(t, t, 2 * B * K); mpz_fdiv_q(mu, t, P);
-    std::vector<uint32_t> ctx(128 + padic_tiles::kImageBytes / 4, 0), pl(K);
+    std::vector<uint32_t> ctx(128 + padic_tiles::kLimbImageBytes / 4, 0), pl(K);
+    static_assert(padic_tiles::kLimbImageBytes >= padic_tiles::kImageBytes, "ctx holds either image");
     to_limbs(P, pl.data(), K);
     for (int j = 0; j < K; j++) ctx[j] = (uint32_t)(-(int32_t)pl[j]);
     to_limbs(mu, ctx.data() + K + 3, K + 1);
@@ -98,7 +100,10 @@ int main(int argc, char **argv) {
     {
         // M37_S1LO=112: the image of code objects generated with the s1lo112 switch (product 1 from column 112)
         // M37_QSHIFT=8: the image of fthe_padic_m37s (product 1's operand shifted by 8 bytes)
-        std::vector<uint8_t> img = padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo,
+        // M37_LIMB=1: the image of fthe_padic_m37l (product 1 fed the limbs as they lie)
+        const bool limb = getenv("M37_LIMB") && atoi(getenv("M37_LIMB"));
+        std::vector<uint8_t> img = limb ? padic_tiles::build_limb(P) :
+                                   padic_tiles::build(P, getenv("M37_S1LO") ? atoi(getenv("M37_S1LO")) : padic_tiles::kS1Lo,
                                                       getenv("M37_QSHIFT") ? atoi(getenv("M37_QSHIFT")) : 0);
         if (img.empty()) { printf("tile image failed\n"); return 2; }
         memcpy(ctx.data() + 128, img.data(), img.size());

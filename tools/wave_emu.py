@@ -9,7 +9,7 @@ workgroup is emulated wave by wave: every wave up to its s_barrier, then each wa
 waves share only what they wrote before the barrier).
 
   python tools/wave_emu.py         (self-test: 16 random adds mod n^2 and edge cases vs Python integers)
-  python tools/wave_emu.py m37     (m37t, m37s: the other bodies; one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
+  python tools/wave_emu.py m37     (m37t, m37s, m37l: the other bodies; one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
 """
 import os
 import random
@@ -805,23 +805,25 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
 
 def _m37_asm(gm, variant):
     """the kernel text of a variant: 'm37' (fthe_padic_m37), 'm37t' (fthe_padic_m37t, the four-tile product 2) or
-    'm37s' (fthe_padic_m37s: m37t with product 1's operand shifted by 8 bytes, 15 tiles)"""
-    assert variant in ('m37', 'm37t', 'm37s')
+    'm37s' (fthe_padic_m37s: m37t with product 1's operand shifted by 8 bytes, 15 tiles) or 'm37l' (fthe_padic_m37l:
+    m37t with product 1 fed the limbs as they lie)"""
+    assert variant in ('m37', 'm37t', 'm37s', 'm37l')
     return gm.gen_padic_mfma('fthe_padic_' + variant, top_est=variant != 'm37',
-                             q1_shift=gm.Q1_SHIFT if variant == 'm37s' else 0)
+                             q1_shift=gm.Q1_SHIFT if variant == 'm37s' else 0, limb_op=variant == 'm37l')
 
 
 def _m37_ctx(gm, mm, P, s1_lo, variant):
     """the key context: -P limbs, Pt = P >> 1000 (m37t, m37s), the tile image (m37s: the shifted layout)"""
     K, B = 37, 28
-    ctx = bytearray(gm.TILE_OFF + gm.TILE_BYTES)
+    ctx = bytearray(gm.TILE_OFF + (gm.TILE_BYTES_L if variant == 'm37l' else gm.TILE_BYTES))
     for j in range(K):                                           # -P limbs (int32)
         ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
     if variant != 'm37':
         assert P.bit_length() <= gm.TOPEST_MAX_BITS == mm.TOPEST_MAX_BITS
         ctx[gm.PT_OFF:gm.PT_OFF + 4] = (P >> gm.PT_SHIFT).to_bytes(4, 'little')
     assert gm.Q1_SHIFT == mm.Q1_SHIFT
-    img = mm.MfmaKey(P, s1_lo=s1_lo, q_shift=mm.Q1_SHIFT if variant == 'm37s' else 0).tile_image()
+    img = mm.MfmaKey(P, s1_lo=s1_lo, q_shift=mm.Q1_SHIFT if variant == 'm37s' else 0,
+                     limb_op=variant == 'm37l').tile_image()
     ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
     return ctx
 
@@ -878,7 +880,9 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None, ju
         (L * 4).to_bytes(4, 'little') + (S * L * 4).to_bytes(4, 'little') + L.to_bytes(4, 'little') + \
         (1).to_bytes(4, 'little') + bytes(128)
     mem.alloc(karg, KA)
-    junk = {60 + w: [rng.getrandbits(32) for _ in range(64)] for w in (0, 1, 37, 38, 39)} if junk_pads else None
+    # m37l: the pad registers beside T[36..73] and V[36..73]
+    pads = (136, 175, 212, 251) if variant == 'm37l' else (60, 61, 97, 98, 99)
+    junk = {r: [rng.getrandbits(32) for _ in range(64)] for r in pads} if junk_pads else None
     steps = run_workgroup(asm, lds_bytes, 4, mem, KA, 0, nv, finish=(0,), junk=junk)
     bad = 0
     for g_ in range(64):
@@ -974,7 +978,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'nadicb':
         sys.exit(1 if nadicb_selftest(waves=int(sys.argv[2]) if len(sys.argv) > 2 else 1) else 0)
-    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s'):
+    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s', 'm37l'):
         sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None, variant=sys.argv[1]) else 0)
     elif len(sys.argv) > 1:                   # e.g. 211: wave 0 takes a second batch (the grid-stride loop)
         selftest(ntests=int(sys.argv[1]), count0=int(sys.argv[1]))
