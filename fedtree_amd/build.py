@@ -39,11 +39,12 @@ def build_kernels():
     # A/B generator switches (FTHE_GEN_*: tools/build_m37_ab.sh, the FTHE_GEN_NADIC_AB library A/Bs; some give
     # wrong results by design, e.g. FTHE_GEN_NADIC_AB=noest) reach only a library built elsewhere
     # (FTHE_BUILD_OUT), never the in-tree libfthe.so.  Removed before the generators are imported: some read
-    # their switches at import time.
+    # their switches at import time.  gen_padic_mfma takes its switches as an argument: read below, after the scrub.
     if OUT == DEFAULT_OUT:
         for k in sorted(k for k in os.environ if k.startswith("FTHE_GEN_")):
             os.environ.pop(k)
             sys.stderr.write(f"build.py: ignoring {k} (A/B generator switch) for the in-tree library\n")
+    m37_ab = os.environ.get("FTHE_GEN_M37_AB", "")
     import gen_montprog  # noqa: E402
     import gen_padic  # noqa: E402
     import gen_nadic  # noqa: E402
@@ -64,18 +65,12 @@ def build_kernels():
     for K in (37, 19):
         kernels.append((1000 + K, f"fthe_padic_k{K}", f"padic_k{K}",
                         lambda K=K: gen_padic.gen_padic(K, 28, f"fthe_padic_k{K}")))
-    # the K = 37 P-adic kernel with matrix-core Barrett reductions: pseudo-variant 1137
-    kernels.append((1137, "fthe_padic_m37", "padic_m37", lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37")))
-    # its four-tile body (product 2 of the reductions without its fifth M-tile): pseudo-variant 1237
-    kernels.append((1237, "fthe_padic_m37t", "padic_m37t",
-                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37t", top_est=True)))
-    # the four-tile body on product 1's operand shifted by 8 bytes (15 instead of 19 product-1 tiles): 1337
-    kernels.append((1337, "fthe_padic_m37s", "padic_m37s",
-                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37s", top_est=True,
-                                                          q1_shift=gen_padic_mfma.Q1_SHIFT)))
-    # the four-tile body with product 1 fed q1's limbs as they lie (no repack before product 1): 1437
-    kernels.append((1437, "fthe_padic_m37l", "padic_m37l",
-                    lambda: gen_padic_mfma.gen_padic_mfma("fthe_padic_m37l", top_est=True, limb_op=True)))
+    # the K = 37 P-adic kernel with matrix-core Barrett reductions: pseudo-variant 1137; its four-tile body (product 2
+    # of the reductions without its fifth M-tile): 1237; the four-tile body on product 1's operand shifted by 8 bytes
+    # (15 instead of 19 product-1 tiles): 1337; with product 1 fed q1's limbs as they lie (no repack): 1437
+    for S, body in ((1137, "m37"), (1237, "m37t"), (1337, "m37s"), (1437, "m37l")):
+        kernels.append((S, f"fthe_padic_{body}", f"padic_{body}",
+                        lambda body=body: gen_padic_mfma.gen_body(body, m37_ab)))
     # the n-adic four-lane kernel of the public-key encrypt (base-n digits of 76 limbs): pseudo-variant 2076
     kernels.append((2076, "fthe_nadic_q76", "nadic_q76", lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_q76")))
     # its Montgomery form (LSB-first reductions, no quotient estimates): pseudo-variant 2176

@@ -283,8 +283,6 @@ struct fthe_ctx {
     hipFunction_t fn[MAX_VARIANTS] = {};
     hipModule_t mod_addb = nullptr;           // fthe_addb_q152 (gen_addb.py): P-2048 adds, matrix-core Barrett
     hipFunction_t fn_addb = nullptr;
-    uint32_t *d_jobctr = nullptr;             // job counters of persistent launches (one per launch, in turn)
-    unsigned jobctr_i = 0;
     DevBuf slots, slots1, scratch, io[5];   // slots1: the small-modulus (mod p, q) programs
     size_t mem_limit = 0;                   // fthe_ctx_set_mem_limit: cap on the slot region grown for a call
     DevBuf hb[6];                           // histogram CSR / segmented-product plan (device)
@@ -623,7 +621,6 @@ extern "C" void fthe_ctx_destroy(fthe_ctx *c) {
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (int i = 0; i < MAX_VARIANTS; i++) if (c->mod[i]) (void)hipModuleUnload(c->mod[i]);
     if (c->mod_addb) (void)hipModuleUnload(c->mod_addb);
-    if (c->d_jobctr) (void)hipFree(c->d_jobctr);
     if (c->cub_tmp) (void)hipFree(c->cub_tmp);
     for (auto &e : c->prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1546,7 +1543,7 @@ int launch_montprog(fthe_ctx *c, void *slots, int S, int L, const void *prog, co
     if (nrows > 16) return FTHE_ERR_ARG;
     for (int i = 0; i < nrows; i++) args.rows[i] = rows[i];
 #ifdef FTHE_STAMP_HOOK
-    // timing builds only (FTHE_GEN_M37_AB=stamp, tools/m37_stamps.py; compiled in for FTHE_BUILD_OUT libraries,
+    // timing builds only (generator switch stamp, tools/m37_stamps.py; compiled in for FTHE_BUILD_OUT libraries,
     // never the in-tree one): FTHE_STAMP_PTR = a device buffer of FTHE_STAMP_LAUNCHES x 128 KiB, one 128 KiB
     // record area per launch in turn
     static const char *stamp_ptr = getenv("FTHE_STAMP_PTR");
@@ -1567,10 +1564,6 @@ int launch_montprog(fthe_ctx *c, void *slots, int S, int L, const void *prog, co
     // only the workgroups that hold live elements (slot strides stay those of L)
     if (live > (size_t)L) return FTHE_ERR_ARG;
     if (live == 0) return FTHE_OK;
-    // fthe_padic_m37 built with dynamic jobs (FTHE_GEN_M37_AB=dyn, A/B under FTHE_M37_DYN=1): the resident
-    // workgroups only, a zeroed job counter per launch (gen_padic_mfma.py DYN)
-    static const bool m37_dyn = getenv("FTHE_M37_DYN") && *getenv("FTHE_M37_DYN") == '1';
-    const bool dyn = mfma && m37_dyn && nrows < 15;
     const bool nb = kVariants[vi].S == kNadicBarS;       // kNbPerWg ciphertexts per workgroup of kNbWaves waves
     if (nb && L % kNbPerWg) return FTHE_ERR_ARG;          // the kernel covers whole workgroups of the slots
     unsigned blocks = nb ? (unsigned)((live + kNbPerWg - 1) / kNbPerWg)
@@ -1578,14 +1571,6 @@ int launch_montprog(fthe_ctx *c, void *slots, int S, int L, const void *prog, co
     if (nb) {                     // persistent: at most one workgroup per CU, batches from its LDS counter
         blocks = std::min(blocks, (unsigned)c->n_cu);
         args.pad = blocks;
-    }
-    if (dyn) {
-        if (!c->d_jobctr) HIPOK(hipMalloc(&c->d_jobctr, 256 * sizeof(uint32_t)));
-        blocks = std::min(blocks, 2u * (unsigned)c->n_cu);          // 249 VGPRs: two waves per SIMD
-        uint32_t *ctr = c->d_jobctr + (c->jobctr_i++ % 256);
-        args.pad = 4 * blocks;
-        args.rows[14] = ctr;
-        if (hipMemsetAsync(ctr, 0, sizeof(uint32_t), st) != hipSuccess) return FTHE_ERR_HIP;
     }
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     if (c->prof) {

@@ -40,6 +40,8 @@ and fthe_padic_m37s (top_est=True, q1_shift=8), the same with product 1's operan
 the four tiles with m - k = 1: 15 product-1 tiles, and the image of padic_tiles::build(P, 128, 8).
 A fourth, fthe_padic_m37l (top_est=True, limb_op=True), feeds product 1 the radix-2^28 limbs of q1 as they lie -- no
 repack into base-256 dwords, the tilted band in 15 tiles of their own: the 24 KB image of padic_tiles::build_limb(P).
+BODIES holds the four argument sets and gen_body(variant, ab) generates one by name; the A/B switches (SWITCHES) are
+the argument ab of either, parsed by parse_ab.
 """
 import os
 import sys
@@ -47,68 +49,60 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gen_montprog import _descriptor  # noqa: E402
 
-# A/B variants for tools/build_m37_ab.sh only (fedtree_amd/build.py clears the switch): the timing-only ones
-# give wrong results (noswap, nonop, nomfma); the others are correct schedules: nodbuf, nointerleave, nopair,
-# noprepair, nodesync, spill, pingpong[,ppodd], col3 / col4, marginN, prioN / noprio, noprexor, nocmerge,
-# ldsx[,ldsxa]
-AB = os.environ.get("FTHE_GEN_M37_AB", "")
 TILE_OFF = 512                  # byte offset of the tile image in ctx
 TILE_BYTES = 20 * 1024          # 19 tiles of 1 KB, padded to 5 dwordx4 per thread
-SPILL_BYTES = 10 * 1024         # per wave: V[37..73] while Barrett 1 runs (9 x dwordx4 + 1 dword per lane)
-SPILL = "spill" in AB           # measured: no gain (profiles/r02zzi_spill_ab.jsonl), so off
-# ping-pong halves in 512-thread workgroups (s_barrier between products and reduction): no gain
-# (profiles/r03t_m37_pingpong_ab.jsonl), so off
-PP = "pingpong" in AB
-# VALU instructions kept between a tile's last MFMA and the lane exchange that reads its results (>= 24: the
-# 8-pass XDL -> VALU hazard then needs no s_nop); A/B knob marginN (24..90 within noise,
-# profiles/r03zj_m37_margin_ab.jsonl)
-MARGIN = next((int(t[6:]) for t in AB.split(',') if t.startswith('margin') and t[6:].isdigit()), 30)
-assert MARGIN >= 24
-# the limbs that only ever reach the matrix cores (the upper product halves and q3) leave the column tails /
-# chunk folds with bit 7 of every byte already flipped (v_bitop3_b32 (x & mask) ^ pattern in place of the
-# mask), so packing them into the b ^ 0x80 operand bytes needs no v_xor per dword: 128 fewer VALU per
-# squaring, 71.7-72.2 vs 73.0-73.5 ms (profiles/r03y_m37_prexor_ab.jsonl)
-PREXOR = "noprexor" not in AB
-# a chunk's carry enters the next chunk's first multiply-add (no carry add in its tail): 162 fewer VALU per
-# squaring, 69.8-70.5 vs 71.7-72.9 ms (profiles/r03za_m37_cmerge_ab.jsonl)
-CMERGE = "nocmerge" not in AB
-# ldsx: the B operands' lane-half exchange through LDS (each half writes the 4 dwords per K-block the other half
-# needs under a half EXEC mask and reads the partner's back) instead of 20 v_permlane32_swap per product, which
-# cost 8 issue cycles each (profiles/r03zr_mfma_hold_probe.jsonl).  Measured slower: 72.1-72.4 vs 70.9-71.0 ms,
-# with ldsxa 74.6-75.3 (profiles/r03zs_m37_ldsx_ab.jsonl): the stores' VGPR transfer and the round trip the
-# wave waits out cost more than the swaps, so off
-LDSX = "ldsx" in AB
-# ldsxa (with ldsx): also the accumulator exchange of every fully paired M-tile (8 of a Barrett's 10): the 8
-# pairs packed into the tile's first 8 accumulator registers, 2 dwordx4 per half through LDS for 8 swaps
-LDSXA = LDSX and "ldsxa" in AB
-LDSX_BYTES = 5 * 1024           # per wave: 5 K-blocks x 64 lanes x 16 B
-# kara: a squaring's cross term V = 2 x0 x1 by one level of Karatsuba on the halves x = xL + xH b^19 (19 / 18
-# limbs): 2 P0 = 2 xL yL and 2 P2 = 2 xH yH normalised first (P0 into V[0..18] and C, P2 complemented into
-# V[38..73]), then the middle columns of (x0L + x0H)(2 x1L + 2 x1H) - 2 P0 - 2 P2 added at b^19 with a biased
-# carry, and the carry rippled through V[57..73] beside x0^2's multiply-adds: 1,046 instead of 1,369
-# multiply-adds per squaring, 4,076 instead of 4,102 VALU (see kara_cross below).  Measured +0.5%: 133.8-134.1 vs
-# 134.5-134.9 ms per 786,432 lanes, 67.8-68.4 vs 68.0-68.5 per 393,216 (profiles/r05i_m37_kara_ab.jsonl) -- the
-# MAD cycles saved mostly reappear as exposed latency of the matrix phases; nokara keeps the plain product (A/B)
-KARA = "nokara" not in AB
-assert not (KARA and LDSX)
-assert not (LDSX and (PP or SPILL))
-LDS_BYTES = TILE_BYTES + (4 * SPILL_BYTES if SPILL else 0) + (4 * LDSX_BYTES if LDSX else 0)
 # product 1's window starts at column 128, not 112: the numerator stays within (Pi - 2^1047, Pi) of Pi = q1 mu
 # (tools/padic_mfma_model.py), which is all Barrett asks, and the 16 columns no longer formed are M-tile 4's rows
-# 16..31 (columns 272..287: zero), which its fold skips; s1lo112 keeps the old window (needs the image of
-# padic_tiles::build(P, 112): A/B in the standalone harness only)
-S1_LO = 112 if "s1lo112" in AB else 128     # product-1 columns S1_LO .. S1_LO + 159
+# 16..31 (columns 272..287: zero), which its fold skips
+S1_LO = 128                     # product-1 columns S1_LO .. S1_LO + 159 (the s1lo112 switch: 112, see s1_lo)
 S1_TOP = 272                    # q1 mu has no column above 271
-# the second reduction's q3 (it only feeds product 2) is folded straight into product 2's operand dwords, radix
-# 2^32 from bit QBIT - 8, in place of 28-bit limbs repacked by orpack; noq3dw keeps the limb fold
-Q3DW = "noq3dw" not in AB and not LDSX
 QBIT = 28 * 38                  # q3 = floor(N / 2^1064)
-# clampbr: Barrett 1's sign-keyed clamp (37 v_bitop3) is skipped by a wave-uniform branch when no lane's numerator
-# went negative (q1 = 0, or a tiny q1 at P near 2^1030); the mask itself is still formed (the four-tile body's h reads
-# it).  On in fthe_padic_m37l (noclampbr: off), off in the older bodies (clampbr: on); DESIGN 15 has the measurement
-CLAMPBR_ON, CLAMPBR_OFF = "clampbr" in AB.split(','), "noclampbr" in AB.split(',')
 TILE_D1 = (-3, -2, -1, 0, 1)    # product-1 Toeplitz tiles (k <= 3) by m - k; then k = 4 for m = 0..4
 TILE_D2 = (0, 1, 2, 3)          # product-2: k = 0 for m = 0..4 (tiles 10..14), then Toeplitz (k >= 1) by m - k
+
+# A/B switches (the ab argument of gen_padic_mfma / gen_body: a comma-separated string or a set; tools/build_m37_ab.sh
+# and FTHE_BUILD_OUT libraries only, fedtree_amd/build.py passes none to the in-tree library).  Each names what it
+# turns off in the default schedule, or restores of an earlier one; the measurements are in DESIGN.md:
+#   noswap, nonop, nomfma   timing only (wrong results): no accumulator exchange, no wait for the MFMAs, no MFMAs
+#   nodbuf, nointerleave    one accumulator set; the next tile's MFMAs not spread through the fold
+#   nopair, noprepair       columns not paired in 32-bit before the fold / before the exchange
+#   nodesync                odd workgroups do not start late
+#   prioN, noprio           s_setprio N (0..3, default 3) / none over the reduction
+#   noprexor                the limbs that only feed the matrix cores are not produced with bit 7 of every operand
+#                           byte already flipped (v_bitop3_b32 in place of the mask), so packing them costs a v_xor
+#                           per dword: 128 more VALU per squaring (profiles/r03y_m37_prexor_ab.jsonl)
+#   nocmerge                a chunk's carry is added in its tail, not in the next chunk's first multiply-add: 162 more
+#                           VALU per squaring (profiles/r03za_m37_cmerge_ab.jsonl)
+#   nokara                  a squaring's cross term as a plain product, not by Karatsuba (kara_cross below: +0.5%,
+#                           profiles/r05i_m37_kara_ab.jsonl)
+#   s1lo112                 product 1's window from column 112 (needs the image of padic_tiles::build(P, 112): the
+#                           standalone harness and the emulator only)
+#   noq3dw                  the second reduction's q3 as 28-bit limbs repacked by orpack, not folded straight into
+#                           product 2's operand dwords
+#   clampbr, noclampbr      Barrett 1's sign-keyed clamp (37 v_bitop3) behind a wave-uniform branch that skips it
+#                           when no lane's numerator went negative (q1 = 0, or a tiny q1 at P near 2^1030), or not;
+#                           the mask itself is always formed (the four-tile body's h reads it).  Default: BODIES
+#   stamp                   timing build: each wave's start / end realtime and where it ran (tools/m37_stamps.py)
+SWITCHES = ("noswap", "nonop", "nomfma", "nodbuf", "nointerleave", "nopair", "noprepair", "nodesync", "noprio",
+            "noprexor", "nocmerge", "nokara", "s1lo112", "noq3dw", "clampbr", "noclampbr", "stamp")
+PRIOS = tuple(f"prio{n}" for n in range(4))
+
+
+def parse_ab(ab):
+    """the switch string (exact tokens between commas) or set -> frozenset of known switches"""
+    toks = frozenset(t.strip() for t in ab.split(',') if t.strip()) if isinstance(ab, str) else frozenset(ab)
+    unknown = sorted(toks - set(SWITCHES + PRIOS))
+    if unknown:
+        raise ValueError(f"unknown m37 switch {', '.join(unknown)}: known are {', '.join(SWITCHES + PRIOS)}")
+    for group in ({"clampbr", "noclampbr"}, {"noprio", *PRIOS}):
+        if len(toks & group) > 1:
+            raise ValueError(f"m37 switches {', '.join(sorted(toks & group))} contradict each other")
+    return toks
+
+
+def s1_lo(ab=""):
+    """product 1's first column under the switches ab: the window the tile image must be built for"""
+    return 112 if "s1lo112" in parse_ab(ab) else S1_LO
 
 
 def tile_index(prod, m, k, q1_shift=0, limb_op=False):
@@ -140,9 +134,24 @@ Q1_SHIFT = 8                    # fthe_padic_m37s: q1's byte i is fed at K index
 LIMB_PAD = 1                    # fthe_padic_m37l: pad dwords in front of the 38 limbs of product 1's operand
 TILE_BYTES_L = 24 * 1024        # its image: 15 product-1 tiles and product 2's nine
 
+# the bodies: gen_padic_mfma's arguments, and whether Barrett 1's clamp sits behind a branch (clampbr / noclampbr)
+BODIES = {
+    "m37": dict(top_est=False, q1_shift=0, limb_op=False, clampbr=False),
+    "m37t": dict(top_est=True, q1_shift=0, limb_op=False, clampbr=False),
+    "m37s": dict(top_est=True, q1_shift=Q1_SHIFT, limb_op=False, clampbr=False),
+    "m37l": dict(top_est=True, q1_shift=0, limb_op=True, clampbr=True),
+}
 
-def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op: bool = False) -> str:
-    """limb_op (with top_est: fthe_padic_m37l): product 1 reads its B operands straight from the limbs
+
+def gen_body(variant: str, ab="") -> str:
+    """the kernel fthe_padic_<variant> (a key of BODIES) under the switches ab"""
+    body = {k: v for k, v in BODIES[variant].items() if k != "clampbr"}
+    return gen_padic_mfma("fthe_padic_" + variant, ab=ab, **body)
+
+
+def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op: bool = False, ab="") -> str:
+    """ab: A/B switches (SWITCHES above), a comma-separated string or a set.
+    limb_op (with top_est: fthe_padic_m37l): product 1 reads its B operands straight from the limbs
     T[36..73] (V[36..73] in the second reduction) behind LIMB_PAD pad dwords -- K index 4 (t + LIMB_PAD) + j is byte j
     of q1's limb t, fed as b ^ 0x80 for j < 3 and as it is for j = 3; the constant digit rides in byte 3 of limb 37
     (always zero: T < 2^2068) -- so no orpack and no copy precede product 1; the A image (tools/padic_mfma_model.py
@@ -164,20 +173,35 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     plain residue below 3 P^2 (x1 = its quotient); its own reduction keeps the five-tile product 2."""
     K, B = 37, 28
     MASK = (1 << B) - 1
-    assert q1_shift in (0, Q1_SHIFT) and not (q1_shift and (LDSX or S1_LO != 128))
-    assert not limb_op or (top_est and not q1_shift and not (LDSX or SPILL or PP) and S1_LO == 128 and PREXOR and Q3DW)
-    CLAMPBR = CLAMPBR_ON or (limb_op and not CLAMPBR_OFF)
+    flags = dict(top_est=top_est, q1_shift=q1_shift, limb_op=limb_op)
+    body = [b for b in BODIES.values() if all(b[k] == v for k, v in flags.items())]
+    assert body, f"{flags}: not one of BODIES (limb_op and q1_shift = {Q1_SHIFT} need top_est and exclude each other)"
+    ab = parse_ab(ab)
+
+    def refuse(sw, why):
+        if sw in ab:
+            raise ValueError(f"{name}: switch {sw} refused: {why}")
+    if q1_shift or limb_op:
+        refuse("s1lo112", f"the 15-tile image of the {'limb-fed' if limb_op else 'shifted'} operand exists for the "
+               f"window from column {S1_LO} only")
+    if limb_op:
+        refuse("noprexor", "product 1 reads the limbs as they lie, so they must leave the column tails flipped")
+        refuse("noq3dw", "V[36..73] is product 1's operand, so the second q3 has no limbs to land in")
+    PREXOR, CMERGE, KARA, Q3DW = (sw not in ab for sw in ("noprexor", "nocmerge", "nokara", "noq3dw"))
+    s1lo = s1_lo(ab)                             # product-1 columns s1lo .. s1lo + 159
+    CLAMPBR = "clampbr" in ab or (body[0]["clampbr"] and "noclampbr" not in ab)
+    # VALU instructions kept between a tile's last MFMA and the lane exchange that reads its results (>= 24: the
+    # 8-pass XDL -> VALU hazard then needs no s_nop; 24..90 within noise, profiles/r03zj_m37_margin_ab.jsonl)
+    MARGIN = 30
     tile_bytes = TILE_BYTES_L if limb_op else TILE_BYTES
-    lds_bytes = LDS_BYTES - TILE_BYTES + tile_bytes
     QD = q1_shift // 4                           # the operand's first dword
     # ---- VGPR plan ---------------------------------------------------------
     V_TID, V_GOFF = 0, 1
     VA = (2, 6, 10)                              # A-tile buffers v[2:5], v[6:9], v[10:13] (ACC is free)
     # product columns: NCOL adjacent columns side by side (one 64-bit accumulator chain each), two column
     # sets (the tails of one set run inside the next set's multiply-adds)
-    NCOL = next((int(t[3:]) for t in AB.split(',') if t in ('col3', 'col4')), 2)
-    assert NCOL == 2 or not KARA, "col3 / col4 predate the Karatsuba cross term (wrong results, r06s): add nokara"
-    ACC0 = 10 if NCOL == 2 else 2                # v[ACC0 .. ACC0 + 4 NCOL); below v20 either way
+    NCOL = 2
+    ACC0 = 10                                    # v[ACC0 .. ACC0 + 4 NCOL)
     CARRY = ACC0 + 4 * NCOL
     XA = 20                                      # x0 digit (v20..v56); Barrett: accumulators v20..v51
     G0, G1 = XA, XA + 16
@@ -186,10 +210,8 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     TT = 100                                     # T limbs v100..v173
     VV = 174                                     # V limbs v174..v247
     V_LDS = 248                                  # (lane & 63) * 16
-    V_SPILL = 249                                # this wave's spill area + (lane & 63) * 16 (SPILL only)
     PATV = (249, 250)                            # PREXOR: byte-flip patterns of even / odd limbs
-    assert not (SPILL and PREXOR)
-    NVGPR = 250 if SPILL else 251 if PREXOR else 249
+    NVGPR = 251 if PREXOR else 249
     if limb_op:
         # T[36..73] and V[36..73] are product 1's operand blocks: each sits between two pad registers (v136 / v175,
         # v212 / v251) that the lane exchange may swap freely, 40 consecutive registers from an even one
@@ -199,9 +221,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         NVGPR = V_LDS + 3
         assert NVGPR <= 256
     L36 = "v14"                                  # limb_op: the unflipped copy of limb 36 (the remainder's init)
-    V_XW, V_XR = NVGPR, NVGPR + 1                # LDSX: this wave's exchange area + lane * 16, and ^ 512
-    if LDSX:
-        NVGPR += 2
 
     def pat(t):
         """flip pattern of limb t of a packed number (limb t at bit 28 t): bits j with 28 t + j = 7 mod 8"""
@@ -228,13 +247,10 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     D = [f"v{XB + i}" for i in range(40)]
     # ---- SGPR plan ---------------------------------------------------------
     # s[0:1] kernarg, s2 wg id, s[2:3] call target, s[4:5] slots, s[6:7] prog, s[8:9] ctx, s10 limb
-    # stride, s11 slot stride, s[12:13] return address, s[14:15] op/arg, s[16:17] addr, s18 half (PP), s19 counter;
+    # stride, s11 slot stride, s[12:13] return address, s[14:15] op/arg, s[16:17] addr, s19 counter;
     # s20..s27 = 2^0, 2^4, .., 2^28; s28..s34 = -2^0, .., -2^24; -P limbs from s36
     SPOW, SNEG, SNP = 20, 28, 36                   # s35 = 0x0fffffff
     NSGPR = SNP + K
-    SLO, SHI = 74, 76                            # LDSX: EXEC masks of lanes 0-31 / 32-63
-    if LDSX:
-        NSGPR = SHI + 2
     if KARA:                                     # s76..s78: 2, 3, 4 x mask
         NSGPR = 79
     SPT = NSGPR                                  # top_est: Pt = P >> 1000
@@ -260,10 +276,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 
     def e(line):
         sink[-1].append(line)
-
-    def phase():
-        if PP:
-            e('  s_barrier')
 
     def capture(fn):
         sink.append([])
@@ -445,25 +457,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     OPND = [D]                                  # the block the MFMAs read their B operands from
 
     def swap_operands(Dl=D, nk=5):
-        if LDSX:
-            assert nk == 5
-            # lane r + 32's D[8k + j] <-> lane r's D[8k + 4 + j], as the swaps below; LDS executes one wave's
-            # operations in order, and the last one (K-block 4) is never the first tile's first K-block, which
-            # issue_tile's lgkmcnt counts then leave the only exchange operation possibly still in flight
-            lo, hi = f"s[{SLO}:{SLO + 1}]", f"s[{SHI}:{SHI + 1}]"
-            e(f'  s_mov_b64 exec, {lo}')
-            for k in range(5):
-                e(f'  ds_write_b128 v{V_XW}, v[{XB + 8 * k + 4}:{XB + 8 * k + 7}] offset:{1024 * k}')
-            e(f'  s_mov_b64 exec, {hi}')
-            for k in range(5):
-                e(f'  ds_write_b128 v{V_XW}, v[{XB + 8 * k}:{XB + 8 * k + 3}] offset:{1024 * k}')
-            for k in range(5):
-                e(f'  ds_read_b128 v[{XB + 8 * k}:{XB + 8 * k + 3}], v{V_XR} offset:{1024 * k}')
-            e(f'  s_mov_b64 exec, {lo}')
-            for k in range(5):
-                e(f'  ds_read_b128 v[{XB + 8 * k + 4}:{XB + 8 * k + 7}], v{V_XR} offset:{1024 * k}')
-            e('  s_mov_b64 exec, -1')
-            return
         e('  s_nop 1')
         for k in range(nk):
             for j in range(4):
@@ -480,7 +473,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             rd(prod, m, ks[n], n)
 
     GB0, GB1 = TT + 38, TT + 54                  # second accumulator set v[138:153], v[154:169] (T[38..69])
-    GV0, GV1 = VV + 38, VV + 54                  # or v[212:227], v[228:243] (V[38..69], spilled to LDS)
 
     def issue_tile(prod, m, ks, G0x, G1x, prefetched=True):
         """the MFMAs of M-tile m over K-tiles ks (both lane groups) into accumulators G0x, G1x; with
@@ -499,7 +491,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
                 bo = 8 * k + 4 * g
                 b0 = int(OPND[0][bo][1:])
                 assert b0 % 2 == 0 and [int(r[1:]) for r in OPND[0][bo:bo + 4]] == list(range(b0, b0 + 4))
-                if "nomfma" not in AB:
+                if "nomfma" not in ab:
                     e(f'  v_mfma_i32_32x32x32_i8 v[{G}:{G + 15}], v[{buf}:{buf + 3}], v[{b0}:{b0 + 3}], {src_c}')
 
     P1_TOP = [S1_TOP]                            # product 1: the fold reads the columns below this
@@ -509,7 +501,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         product's last column, or what the dword fold needs); product 2 drops matrix column 0 (the constant
         digit's) and the columns above 130"""
         if prod == 1:
-            return {rho for rho in range(32) if S1_LO + 32 * m + rho < P1_TOP[0]}
+            return {rho for rho in range(32) if s1lo + 32 * m + rho < P1_TOP[0]}
         return {rho for rho in range(32) if 1 <= 32 * m + rho <= 130}
 
     def plan(C):
@@ -522,7 +514,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         for rr in range(0, 16, 2):
             ra = 8 * (rr >> 2) + (rr & 3)
             rhos = (ra, ra + 4)
-            if "noprepair" not in AB and all((r in C) == (r + 1 in C) for r in rhos) \
+            if "noprepair" not in ab and all((r in C) == (r + 1 in C) for r in rhos) \
                     and any(r in C for r in rhos):
                 paired.add(rr)
         for rr in range(16):
@@ -531,46 +523,21 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
                 swaps.append(rr)
         return paired, swaps
 
-    def compact(tile):
-        """LDSXA: all 8 even rr paired, the pairs then sit in rr / 2 and move through LDS"""
-        return LDSXA and plan(consumed(*tile))[0] == set(range(0, 16, 2))
-
     def exchange(G0x, G1x, waited=False, tile=None):
         """results -> VALU: wait out the last MFMA writing them (8-pass XDL: 11 wait states on gfx950), pair
         adjacent rows (plan), then exchange the halves of the registers still needed; waited: at least 30
         VALU instructions already separate that MFMA from here"""
-        if "nonop" not in AB and not waited:
+        if "nonop" not in ab and not waited:
             e('  s_nop 7')
             e('  s_nop 7')
             e('  s_nop 7')
         paired, swaps = plan(consumed(*tile))
-        if compact(tile):
-            for rr in range(0, 16, 2):
-                for G in (G0x, G1x):
-                    e(f'  v_lshl_add_u32 v{G + rr // 2}, v{G + rr + 1}, 8, v{G + rr}')
-            # lanes 0-31 send the group-1 pairs and receive the partner's group-0 pairs into them, lanes
-            # 32-63 the other way round (the permlane32_swap of every pair register, as below)
-            lo, hi = f"s[{SLO}:{SLO + 1}]", f"s[{SHI}:{SHI + 1}]"
-            e(f'  s_mov_b64 exec, {lo}')
-            for j in range(2):
-                e(f'  ds_write_b128 v{V_XW}, v[{G1x + 4 * j}:{G1x + 4 * j + 3}] offset:{1024 * j}')
-            e(f'  s_mov_b64 exec, {hi}')
-            for j in range(2):
-                e(f'  ds_write_b128 v{V_XW}, v[{G0x + 4 * j}:{G0x + 4 * j + 3}] offset:{1024 * j}')
-            for j in range(2):
-                e(f'  ds_read_b128 v[{G0x + 4 * j}:{G0x + 4 * j + 3}], v{V_XR} offset:{1024 * j}')
-            e(f'  s_mov_b64 exec, {lo}')
-            for j in range(2):
-                e(f'  ds_read_b128 v[{G1x + 4 * j}:{G1x + 4 * j + 3}], v{V_XR} offset:{1024 * j}')
-            e('  s_mov_b64 exec, -1')
-            e('  s_waitcnt lgkmcnt(0)')
-            return
         for rr in sorted(paired):
             for G in (G0x, G1x):
                 e(f'  v_lshl_add_u32 v{G + rr}, v{G + rr + 1}, 8, v{G + rr}')
         if paired:
             e('  s_nop 1')
-        for rr in (swaps if "noswap" not in AB else []):
+        for rr in (swaps if "noswap" not in ab else []):
             e(f'  v_permlane32_swap_b32_e32 v{G0x + rr}, v{G1x + rr}')
         e('  s_nop 1')
 
@@ -578,16 +545,12 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         """(output column, register, pre-paired) of M-tile m in column order, after exchange()"""
         C = consumed(prod, m)
         paired, _ = plan(C)
-        cp = compact((prod, m))
         out = []
         for rho in sorted(C):
             rr = (rho & 3) + 4 * (rho >> 3)
             if rho % 2 and rr - 1 in paired:
                 continue                              # folded into rho - 1 before the exchange
-            src = rho
-            if cp:                                    # the pair of rr sits in rr / 2 of the same group
-                src = (rr // 2 & 3) + 8 * (rr // 2 >> 2) + 4 * (rho >> 2 & 1)
-            out.append((s_of(rho), creg(src), rho % 2 == 0 and rr in paired))
+            out.append((s_of(rho), creg(rho), rho % 2 == 0 and rr in paired))
         return out
 
     def mtile_mfmas(prod, m, ks, nxt=None):
@@ -602,7 +565,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         rr = (rho & 3) + 4 * (rho >> 3)
         return f"v{(G1x if (rho >> 2) & 1 else G0x) + rr}"
 
-    def run_tiles(tiles, consume, nxt, dbuf, after_issue0=None, setb=None):
+    def run_tiles(tiles, consume, nxt, dbuf, after_issue0=None):
         """all M-tiles of a product: consume(m, col_reg_of_the_tile) after each; dbuf: two accumulator sets,
         tile m+1's MFMAs issued before tile m's results are folded, so the matrix core works while the
         lane does (needs T[38..69] free); tile 0's first A tiles are prefetched by the caller"""
@@ -612,7 +575,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
                 mtile_mfmas(*tiles[m], nxt=tiles[m + 1] if m < nt - 1 else nxt)
                 consume(m, col_reg)
             return
-        sets = ((G0, G1), setb or (GB0, GB1))
+        sets = ((G0, G1), (GB0, GB1))
         issue_tile(*tiles[0], *sets[0])
         separated = False                        # >= 30 VALU instructions after this tile's last MFMA
         if after_issue0 is not None:             # independent VALU work while tile 0 runs
@@ -629,7 +592,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             # tiles after the first were issued inside the previous fold, whose last 40% has no MFMA
             exchange(ga, gb, waited=separated, tile=tuple(tiles[m][:2]))
             fold = capture(lambda: consume(m, lambda rho, ga=ga, gb=gb: col_reg(rho, ga, gb)))
-            if "nointerleave" in AB:
+            if "nointerleave" in ab:
                 for ins in nxt_issue + fold:
                     e(ins)
                 separated = False
@@ -751,7 +714,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         i = 0
         while i < len(cols):
             s_, r_, pr_ = cols[i]
-            if not pr_ and i + 1 < len(cols) and "nopair" not in AB:
+            if not pr_ and i + 1 < len(cols) and "nopair" not in ab:
                 s2_, r2_, pr2_ = cols[i + 1]
                 t1, t2 = (8 * s_ - ch.base) // ch.radix, (8 * s2_ - ch.base) // ch.radix
                 if not pr2_ and s2_ == s_ + 1 and t1 == t2 and 8 * s_ - ch.base - ch.radix * t1 <= 16:
@@ -764,7 +727,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 
     P1_TILES = [(1, m, [k for k in range(5) if m - k <= (0 if q1_shift or limb_op else 1)]) for m in range(5)]
     P2_TILES = [(2, m, [k for k in range(5) if m >= k]) for m in range(5)]
-    assert P1_TILES[0][2][0] != 4 and P2_TILES[0][2][0] != 4      # LDSX: see swap_operands
 
     V_FRAC = XA + 37                            # top_est: f32, the 32 bits of N below QBIT (v57)
     assert V_FRAC not in range(G0, G0 + 32) and V_FRAC not in range(XA + 32, XA + 37) and \
@@ -772,7 +734,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 
     nclamp = [0]
 
-    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, setb=None, pre_in=None, dw=None, t4=False):
+    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, pre_in=None, dw=None, t4=False):
         """product 1: q3 = Barrett's quotient of T (Tl: 2K limbs, Tl[K-1] < 2^29 allowed) -> q3out (K regs,
         may be Tl[K:]); clamp: q3 = -1 (numerator < 0: q1 = 0, or a small q1 at P near 2^1030) -> 0; prefetched: its first A-tile reads are in flight;
         dbuf: double-buffered accumulators (T[38..69] free); pre_in: Tl[K..2K-1] arrive pre-flipped
@@ -807,7 +769,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         if dw is None:
             # chunk -1 is bits 1036..1063 of N: f32 = its 28 bits over four zeros
             tap = {-1: lambda lo: [f'  v_lshlrev_b32_e32 v{V_FRAC}, 4, {lo}']} if t4 else None
-            ch = Chunks(QBIT, (8 * S1_LO - QBIT) // B, 39, q3out, neg=False, px=PREXOR, tap=tap)
+            ch = Chunks(QBIT, (8 * s1lo - QBIT) // B, 39, q3out, neg=False, px=PREXOR, tap=tap)
         else:
             assert not clamp
             base = QBIT - 8                                          # dw[0]'s byte 0 is the constant digit
@@ -826,13 +788,13 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
                     return [f'  v_and_b32_e32 {dw[32]}, {hex((1 << (B * K + 8 - 1024)) - 1)}, {lo}',
                             f'  v_xor_b32_e32 {dw[32]}, 0x80808080, {dw[32]}']
                 return [f'  v_xor_b32_e32 {dw[w]}, 0x80808080, {lo}']
-            ch = Chunks(base, (8 * S1_LO - base) // 32, ndw - 1, None, neg=False, nocarry_last=True, radix=32,
+            ch = Chunks(base, (8 * s1lo - base) // 32, ndw - 1, None, neg=False, nocarry_last=True, radix=32,
                         out=out, tap=tap)
             P1_TOP[0] = (base + ndw * 32) // 8                       # columns from 264 (260) on lie above the last dword
 
         def consume(m, creg):
-            fold_columns(ch, tile_cols(1, m, lambda rho: S1_LO + 32 * m + rho, creg))
-        run_tiles(P1_TILES, consume, P2_TILES[0], dbuf, setb=setb)
+            fold_columns(ch, tile_cols(1, m, lambda rho: s1lo + 32 * m + rho, creg))
+        run_tiles(P1_TILES, consume, P2_TILES[0], dbuf)
         ch.finish()
         OPND[0] = D
         P1_TOP[0] = S1_TOP
@@ -915,12 +877,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e('.p2align 8')
     e(f'.type {name},@function')
     e(f'{name}:')
-    # DYN: persistent waves with dynamic jobs -- the launch holds at most the resident workgroups; job j = the
-    # lanes [64 j, 64 j + 64); a wave's first job is 4 wg + wave (the static mapping), the next ones come from a
-    # device counter (kernarg rows[14], zeroed by the launcher) offset by the waves launched (kernarg 0x24), so
-    # a wave the SIMD's arbiter favours runs more jobs and the launch has no workgroup-granular tail
-    DYN = "dyn" in AB and not PP
-    STAMP = "stamp" in AB                        # timing build: each wave's start / end realtime (100 MHz) and
+    STAMP = "stamp" in ab                        # timing build: each wave's start / end realtime (100 MHz) and
     if STAMP:                                    # where it ran, 16 B at kernarg rows[15] + 16 (4 wg + wave)
         e('  s_memrealtime s[80:81]')
         e('  s_mov_b32 s85, s2')
@@ -928,14 +885,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e('  s_load_dwordx2 s[6:7], s[0:1], 0x8')
     e('  s_load_dwordx2 s[8:9], s[0:1], 0x10')
     e('  s_load_dwordx2 s[10:11], s[0:1], 0x18')
-    if DYN:
-        e('  s_load_dwordx2 s[92:93], s[0:1], 0x20')                  # live lanes, waves launched
-        e('  s_load_dwordx2 s[94:95], s[0:1], 0x98')                  # job counter
     e('  s_waitcnt lgkmcnt(0)')
-    if DYN:
-        e('  s_mov_b64 s[90:91], s[6:7]')                             # the program's first op
-        e('  s_add_u32 s92, s92, 63')
-        e('  s_lshr_b32 s92, s92, 6')                                 # jobs
     off, sreg, rem = 0, SNP, K
     for width in (16, 8, 4, 2, 1):
         while rem >= width:
@@ -958,24 +908,11 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     if PREXOR:
         for v_, val in zip(PATV, PATVAL):
             e(f'  v_mov_b32_e32 v{v_}, {hex(val)}')
-    # PP (ping-pong): 512-thread workgroups, the two waves of a SIMD are waves w and w + 4 of one workgroup;
-    # half 1 runs one phase behind half 0 (s_barrier between the products and the reduction of every
-    # SQR / MUL / LOADP), so one wave's matrix phases meet the other wave's product phase
-    e(f'  s_lshl_b32 s14, s2, {11 if PP else 10}')
-    if PP:
-        e(f'  v_readfirstlane_b32 s18, v{V_TID}')
-        if "ppodd" in AB:                          # s18 = half (odd waves: 1)
-            e('  s_bfe_u32 s18, s18, 0x10006')
-        else:                                      # s18 = half (waves 0-3: 0, waves 4-7: 1)
-            e('  s_lshr_b32 s18, s18, 8')
+    e('  s_lshl_b32 s14, s2, 10')
     e(f'  v_lshlrev_b32_e32 v{V_GOFF}, 2, v{V_TID}')
     e(f'  v_add_u32_e32 v{V_GOFF}, s14, v{V_GOFF}')
     # LDS tile image: 5 x 4 KB, each thread one dwordx4 per 4 KB
-    if PP:                                       # threads t and t + 256 write the same image words
-        e(f'  v_and_b32_e32 v10, 0xff, v{V_TID}')
-        e('  v_lshlrev_b32_e32 v10, 4, v10')
-    else:
-        e(f'  v_lshlrev_b32_e32 v10, 4, v{V_TID}')
+    e(f'  v_lshlrev_b32_e32 v10, 4, v{V_TID}')
     for it in range(tile_bytes // 4096):
         e(f'  global_load_dwordx4 v[2:5], v10, s[8:9] offset:{TILE_OFF}')
         e('  s_waitcnt vmcnt(0)')
@@ -984,36 +921,14 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             e('  v_add_u32_e32 v10, 0x1000, v10')
     e(f'  v_and_b32_e32 v{V_LDS}, 63, v{V_TID}')
     e(f'  v_lshlrev_b32_e32 v{V_LDS}, 4, v{V_LDS}')
-    if SPILL:
-        e(f'  v_lshrrev_b32_e32 v{V_SPILL}, 6, v{V_TID}')             # wave in the workgroup
-        e(f'  v_mul_u32_u24_e32 v{V_SPILL}, {hex(SPILL_BYTES)}, v{V_SPILL}')
-        e(f'  v_add_u32_e32 v{V_SPILL}, {hex(TILE_BYTES)}, v{V_SPILL}')
-        e(f'  v_add_u32_e32 v{V_SPILL}, v{V_SPILL}, v{V_LDS}')
-    if LDSX:
-        e(f'  v_lshrrev_b32_e32 v{V_XW}, 6, v{V_TID}')                # wave in the workgroup
-        e(f'  v_mul_u32_u24_e32 v{V_XW}, {hex(LDSX_BYTES)}, v{V_XW}')
-        e(f'  v_add_u32_e32 v{V_XW}, {hex(TILE_BYTES)}, v{V_XW}')
-        e(f'  v_add_u32_e32 v{V_XW}, v{V_XW}, v{V_LDS}')
-        e(f'  v_xor_b32_e32 v{V_XR}, 0x200, v{V_XW}')                # lane ^ 32
-        e(f'  s_mov_b32 s{SLO}, -1')
-        e(f'  s_mov_b32 s{SLO + 1}, 0')
-        e(f'  s_mov_b32 s{SHI}, 0')
-        e(f'  s_mov_b32 s{SHI + 1}, -1')
     e('  s_waitcnt lgkmcnt(0)')
     e('  s_barrier')
-    if PP:
-        e('  s_cmp_eq_u32 s18, 1')                  # half 1: one barrier ahead = one phase behind
-        e('  s_cbranch_scc0 .Lpp_start')
-        e('  s_barrier')
-        e('.Lpp_start:')
-    elif "nodesync" not in AB:
+    if "nodesync" not in ab:
         # odd workgroups start ~8K cycles late: the two waves of a SIMD then reach their matrix-core
         # phases at different times (s_sleep spends no issue slots); 1.5% (profiles/r02zt_desync_ab.jsonl)
         e('  s_bitcmp1_b32 s2, 0')
         e('  s_cbranch_scc0 .Ldesync_done')
-        nsl = int(os.environ.get("FTHE_GEN_M37_SLEEPS", "1"))
-        for _ in range(nsl):
-            e('  s_sleep 127')
+        e('  s_sleep 127')
         e('.Ldesync_done:')
 
     e('.Lprog:')
@@ -1168,9 +1083,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             col['terms'] = [(sq, sq)]
         cols.append(col)
     columns(cols, bg=rip)
-    phase()
     call('.Lreduce')
-    phase()
     e('  s_sub_u32 s19, s19, 1')
     e('  s_branch .Lsqr_loop')
 
@@ -1182,15 +1095,12 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     TM = X1 + T[K:]                              # x1, y1 dead
     columns(product_cols(X0, Y0, 2 * K, TM))
     move(T[:K], X1)
-    phase()
     call('.Lreduce')
-    phase()
     e('  s_branch .Lprog')
 
     # LOADP slot: plain X -> T -> (q3 = x1, r = x0)
     e('.Lloadp:')
     load_limbs(T)
-    phase()
     Q = D[2:2 + K]                               # limb_op: the first reduction's q3 limbs
     RINIT = (lambda Tl: Tl[:K - 1] + [L36]) if limb_op else (lambda Tl: None)
     if limb_op:
@@ -1201,7 +1111,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     else:
         q3 = mfma_barrett(T, T[K:], clamp=True, pre_in=False)
         mfma_remainder(T, q3, T[:K], nxt_p1=False)
-    phase()
     move(X0, T[:K])
     if limb_op:
         move(X1, T[K:2 * K])
@@ -1227,29 +1136,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e('  s_branch .Lprog')
 
     e('.Lend:')
-    if DYN:
-        e('  s_mov_b64 exec, 1')
-        e('  v_mov_b32_e32 v2, 0')
-        e('  v_mov_b32_e32 v3, 1')
-        e('  global_atomic_add v4, v2, v3, s[94:95] sc0')
-        e('  s_waitcnt vmcnt(0)')
-        e('  s_mov_b64 exec, -1')
-        e('  v_readfirstlane_b32 s96, v4')
-        e('  s_add_u32 s96, s96, s93')                                # job = waves launched + draw
-        e('  s_cmp_ge_u32 s96, s92')
-        e('  s_cbranch_scc1 .Ljobs_done')
-        e('  s_lshl_b32 s96, s96, 8')
-        e(f'  v_and_b32_e32 v2, 63, v{V_TID}')
-        e('  v_lshlrev_b32_e32 v2, 2, v2')
-        e(f'  v_add_u32_e32 v{V_GOFF}, s96, v2')
-        e('  s_mov_b64 s[6:7], s[90:91]')
-        e('  s_branch .Lprog')
-        e('.Ljobs_done:')
-    if PP:                                       # half 0 pays back half 1's extra barrier
-        e('  s_cmp_eq_u32 s18, 0')
-        e('  s_cbranch_scc0 .Lpp_end')
-        e('  s_barrier')
-        e('.Lpp_end:')
     if STAMP:
         e('  s_waitcnt vmcnt(0)')
         e('  s_memrealtime s[82:83]')
@@ -1261,7 +1147,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         e('  s_cbranch_scc1 .Lstamp_done')
         e('  s_mov_b64 exec, 1')
         e(f'  v_lshrrev_b32_e32 v2, 6, v{V_TID}')
-        e(f'  v_lshl_add_u32 v2, s85, {3 if PP else 2}, v2')             # wave index in the launch
+        e('  v_lshl_add_u32 v2, s85, 2, v2')                           # wave index in the launch
         e('  v_lshlrev_b32_e32 v7, 4, v2')
         e('  v_mov_b32_e32 v2, s80')
         e('  v_mov_b32_e32 v3, s82')
@@ -1275,18 +1161,12 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     # reduce (SQR, MUL): T (x0^2 or x0 y0), V (cross terms) -> x0 = T mod P, x1 = (V + T div P) mod P
     e('.Lreduce:')
     # default s_setprio 3 over the reduction (noprio: none): -0.5..1% (profiles/r03s_m37_prio_ab.jsonl)
-    PRIO = next((int(t[4:]) for t in AB.split(',') if t.startswith('prio') and t[4:].isdigit()),
-                0 if "noprio" in AB else 3)
+    PRIO = next((int(t[4:]) for t in ab & set(PRIOS)), 0 if "noprio" in ab else 3)
     if PRIO:
         e(f'  s_setprio {PRIO}')                # the latency-bound matrix phases win the SIMD's VALU issue
-    dbuf = "nodbuf" not in AB
-    spill = dbuf and SPILL
-    if spill:
-        # V[37..73] waits in LDS while Barrett 1 runs, so its product 1 gets a second accumulator set too
-        for j in range(9):
-            e(f'  ds_write_b128 v{V_SPILL}, v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}] offset:{1024 * j}')
-        e(f'  ds_write_b32 v{V_SPILL}, {V[K]} offset:{9 * 1024}')
-    q3 = mfma_barrett(T, Q if limb_op else T[K:], clamp=True, dbuf=spill, setb=(GV0, GV1), t4=top_est)    # u1 -> T[K..2K-1]
+    dbuf = "nodbuf" not in ab
+    # the first product 1 has one accumulator set: T[38..69] is its operand (limb_op) or takes its q3, and V is live
+    q3 = mfma_barrett(T, Q if limb_op else T[K:], clamp=True, t4=top_est)    # u1 -> T[K..2K-1]
 
     def add_u1():
         for i in range(K):
@@ -1294,10 +1174,6 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
                 e(f'  v_xad_u32 {V[i]}, {q3[i]}, {pat(i)}, {V[i]}')
             else:
                 e(f'  v_add_u32_e32 {V[i]}, {V[i]}, {q3[i]}')  # V += u1 (limbs < 2^29); u1 dies here
-        if spill:                                           # V[37..73] back (older than every tile read)
-            for j in range(9):
-                e(f'  ds_read_b128 v[{VV + 38 + 4 * j}:{VV + 41 + 4 * j}], v{V_SPILL} offset:{1024 * j}')
-            e(f'  ds_read_b32 {V[K]}, v{V_SPILL} offset:{9 * 1024}')
     mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True,
                    inits=RINIT(T))               # u0 -> T[0..K-1]
     if Q3DW:
@@ -1315,19 +1191,16 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e(f'.Lfunc_end_{name}:')
     e(f'  .size {name}, .Lfunc_end_{name}-{name}')
     e('')
-    o.extend(_descriptor(name, lds_bytes, NVGPR, 98 if DYN else 90 if STAMP else NSGPR,
-                         max_wg=512 if PP else 256).splitlines())
+    o.extend(_descriptor(name, tile_bytes, NVGPR, 90 if STAMP else NSGPR).splitlines())
     return "\n".join(o) + "\n"
 
 
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument('--name', default='fthe_padic_m37')
-    ap.add_argument('--top-est', action='store_true', help='the four-tile body (fthe_padic_m37t)')
-    ap.add_argument('--q1-shift', type=int, default=0, help='8 with --top-est: the shifted operand (fthe_padic_m37s)')
-    ap.add_argument('--limb-op', action='store_true', help='with --top-est: the limb-fed product 1 (fthe_padic_m37l)')
+    ap.add_argument('--body', default='m37', choices=sorted(BODIES), help='the kernel fthe_padic_<body>')
+    ap.add_argument('--ab', default='', help='A/B switches, comma-separated: ' + ', '.join(SWITCHES) + ', prioN')
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:
-        f.write(gen_padic_mfma(a.name, top_est=a.top_est, q1_shift=a.q1_shift, limb_op=a.limb_op))
+        f.write(gen_body(a.body, a.ab))

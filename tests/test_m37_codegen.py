@@ -25,7 +25,7 @@ PAT = (0x00808080, 0x08080808)       # limb t of a packed number (at bit 28 t): 
 
 
 def _asm():
-    return g.gen_padic_mfma("fthe_padic_m37")
+    return g.gen_body("m37")
 
 
 def _sections(asm):

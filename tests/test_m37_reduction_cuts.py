@@ -26,20 +26,9 @@ PARENT_VALU, PARENT_SWAPS = 4076, 230            # the schedule before these cut
 
 
 def _counts(ab=""):
-    import importlib
     import gen_padic_mfma as g
     from test_m37_codegen import _sections
-    saved = os.environ.get("FTHE_GEN_M37_AB")
-    os.environ["FTHE_GEN_M37_AB"] = ab
-    try:
-        asm = importlib.reload(g).gen_padic_mfma("fthe_padic_m37")
-    finally:
-        if saved is None:
-            os.environ.pop("FTHE_GEN_M37_AB", None)
-        else:
-            os.environ["FTHE_GEN_M37_AB"] = saved
-        importlib.reload(g)
-    s = _sections(asm)
+    s = _sections(g.gen_body("m37", ab))
     body = s[".Lsqr_loop"] + s[".Lreduce"]
     return (sum(1 for i in body if i.startswith("v_") and "mfma" not in i),
             sum(1 for i in body if i.startswith("v_permlane32_swap")),

@@ -35,7 +35,7 @@ P_WIDE = (1 << 1027) - (1 << 600) + 1
 
 
 def _asm():
-    return g.gen_padic_mfma("fthe_padic_m37l", top_est=True, limb_op=True)
+    return g.gen_body("m37l")
 
 
 def _flat(asm):
@@ -53,8 +53,8 @@ def _counts(asm):
 
 def test_defaults_reproduce_the_three_bodies():
     assert g.gen_padic_mfma("fthe_padic_m37", limb_op=False) == open(os.path.join(GEN, "padic_m37.s")).read()
-    t = g.gen_padic_mfma("fthe_padic_m37t", top_est=True)
-    s = g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8)
+    t = g.gen_body("m37t")
+    s = g.gen_body("m37s")
     assert t == g.gen_padic_mfma("fthe_padic_m37t", top_est=True, limb_op=False)
     assert s == g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8, limb_op=False)
     a = _asm()
@@ -70,14 +70,14 @@ def test_defaults_reproduce_the_three_bodies():
 
 
 def test_squaring_instruction_counts():
-    assert _counts(g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8)) == (M37S_VALU, 208, 100, 60)
+    assert _counts(g.gen_body("m37s")) == (M37S_VALU, 208, 100, 60)
     valu, swaps, mfma, loadp = _counts(_asm())
     assert mfma == 100
     assert swaps == 208                                      # the pads need no swap of their own
     assert valu <= M37S_VALU - 120 and valu == 3785          # 3,914 - 130 + v_cmp; 37 of them behind the branch
     assert loadp == 60
     red = lambda a: sum(1 for i in _sections(a)[".Lreduce"] if i.startswith("v_"))
-    assert red(g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8)) - red(_asm()) == 129
+    assert red(g.gen_body("m37s")) - red(_asm()) == 129
 
 
 def test_the_clamp_sits_behind_a_wave_uniform_branch():
@@ -93,14 +93,7 @@ def test_the_clamp_sits_behind_a_wave_uniform_branch():
     after = _sections_by_label(asm)[".Lnoclamp2"]
     assert after[0].startswith("v_xad_u32")                  # V += u1 follows on both paths
     assert any("v_and_b32_e32" in x and "v56" in x for x in after)     # the four-tile body's h reads the mask
-    os.environ["FTHE_GEN_M37_AB"] = "noclampbr"
-    try:
-        import importlib
-        g2 = importlib.reload(g)
-        plain = g2.gen_padic_mfma("fthe_padic_m37l", top_est=True, limb_op=True)
-    finally:
-        del os.environ["FTHE_GEN_M37_AB"]
-        importlib.reload(g)
+    plain = g.gen_body("m37l", "noclampbr")
     assert "Lnoclamp" not in plain and _counts_by_label(plain)[0] == 3784
     assert [x for x in _flat(asm).splitlines() if x not in set(plain.splitlines())] == \
         ["  v_cmp_ne_u32_e32 vcc, 0, v58", "  s_cbranch_vccz .Lnoclamp1",
@@ -166,7 +159,7 @@ def test_nothing_is_packed_before_product_1():
     sq = _sections(_asm())[".Lsqr_loop"]
     assert sum(1 for i in sq if "0x1808080" in i) == 2                          # T[73] and V[73]
     assert not any(re.search(r"\bv254\b", i) for i in sq)                       # no pat(odd) in the product phase
-    m37s = g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8)
+    m37s = g.gen_body("m37s")
     assert any(re.search(r"\bv250\b", i) for i in _sections(m37s)[".Lsqr_loop"])
 
 

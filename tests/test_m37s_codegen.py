@@ -31,14 +31,14 @@ M37T_VALU = 3924
 
 
 def _asm():
-    return g.gen_padic_mfma("fthe_padic_m37s", top_est=True, q1_shift=8)
+    return g.gen_body("m37s")
 
 
 def test_defaults_reproduce_the_two_bodies():
     assert g.Q1_SHIFT == 8
     assert g.gen_padic_mfma("fthe_padic_m37", q1_shift=0) == open(os.path.join(GEN, "padic_m37.s")).read()
     assert g.gen_padic_mfma("fthe_padic_m37") == open(os.path.join(GEN, "padic_m37.s")).read()
-    t = g.gen_padic_mfma("fthe_padic_m37t", top_est=True)
+    t = g.gen_body("m37t")
     assert t == g.gen_padic_mfma("fthe_padic_m37t", top_est=True, q1_shift=0)
     s = _asm()
     assert s == _asm() and s != t.replace("fthe_padic_m37t", "fthe_padic_m37s")
@@ -52,7 +52,7 @@ def test_defaults_reproduce_the_two_bodies():
 
 
 def test_squaring_instruction_counts():
-    assert _counts(g.gen_padic_mfma("fthe_padic_m37t", top_est=True)) == (M37T_VALU, 208, 116, 68)
+    assert _counts(g.gen_body("m37t")) == (M37T_VALU, 208, 116, 68)
     valu, swaps, mfma, loadp = _counts(_asm())
     assert mfma == 100
     assert swaps == 208
@@ -86,7 +86,7 @@ def test_product_1_reads_15_tiles():
         assert sorted(p1[:5]) == [0, 1, 2, 4, 5], p1[:5]
         assert sorted(p1[:15]) == sorted([4, 2, 1, 0, 5, 3, 2, 1, 6, 3, 2, 7, 3, 8, 9])
     # fthe_padic_m37t reads 19
-    t = _sections(g.gen_padic_mfma("fthe_padic_m37t", top_est=True))[".Lloadp"]
+    t = _sections(g.gen_body("m37t"))[".Lloadp"]
     assert len([i for i in t if i.startswith("ds_read_b128") and int(i.rsplit("offset:", 1)[1]) < 10 * 1024]) == 19
 
 

@@ -35,22 +35,22 @@ def _counts(asm):
 def test_committed_kernels_are_the_generator_output():
     assert g.gen_padic_mfma("fthe_padic_m37") == open(os.path.join(GEN, "padic_m37.s")).read()
     assert g.gen_padic_mfma("fthe_padic_m37", top_est=False) == open(os.path.join(GEN, "padic_m37.s")).read()
-    t = g.gen_padic_mfma("fthe_padic_m37t", top_est=True)
+    t = g.gen_body("m37t")
     assert t == g.gen_padic_mfma("fthe_padic_m37t", top_est=True)
     built = os.path.join(GEN, "padic_m37t.s")
     if os.path.exists(built):
         assert t == open(built).read()
     # outside the reduction's subroutine and the names, the two bodies are the same text but for the load of Pt
-    base = g.gen_padic_mfma("fthe_padic_m37")
+    base = g.gen_body("m37")
     head = lambda a: a.split(".Lreduce:")[0].replace("fthe_padic_m37t", "fthe_padic_m37").splitlines()
     extra = [x for x in head(t) if x not in set(head(base))]
     assert extra == [f"  s_load_dword s79, s[8:9], {hex(g.PT_OFF)}"], extra
 
 
 def test_squaring_instruction_counts():
-    base = _counts(g.gen_padic_mfma("fthe_padic_m37"))
+    base = _counts(g.gen_body("m37"))
     assert base == (M37_VALU, M37_SWAPS, M37_MFMA, 68)
-    valu, swaps, mfma, loadp = _counts(g.gen_padic_mfma("fthe_padic_m37t", top_est=True))
+    valu, swaps, mfma, loadp = _counts(g.gen_body("m37t"))
     assert mfma == 116
     assert swaps <= 212 and swaps == 208
     assert valu <= M37_VALU and valu == 3924
@@ -58,7 +58,7 @@ def test_squaring_instruction_counts():
 
 
 def test_registers_and_the_fraction_register():
-    asm = g.gen_padic_mfma("fthe_padic_m37t", top_est=True)
+    asm = g.gen_body("m37t")
     nv = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", asm).group(1))
     ns = int(re.search(r"\.amdhsa_next_free_sgpr (\d+)", asm).group(1))
     assert nv <= 256 and ns == 80

@@ -2,11 +2,11 @@
 # A/B/... of fthe_padic_m37 code objects in the standalone harness (tools/bin/test_padic, checked against
 # GMP on sampled lanes), round-robin over the variants three times; stops at the first failure.
 #   bash tools/m37_ab.sh TAG V1 V2 [V3 ...]     (tools/bin/m37_V.hsaco; lanes: M37_LANES, default 393216)
-# A variant named t or t_* holds the four-tile body fthe_padic_m37t (gen_padic_mfma.py --top-est), so
+# A variant named t or t_* holds the four-tile body fthe_padic_m37t (gen_padic_mfma.py --body m37t), so
 #   bash tools/m37_ab.sh TAG base t     runs m37 and m37t round-robin in one series.
-# A variant named s or s_* holds fthe_padic_m37s (--top-est --q1-shift 8) and reads the shifted tile image:
+# A variant named s or s_* holds fthe_padic_m37s (--body m37s) and reads the shifted tile image:
 #   bash tools/m37_ab.sh TAG t s
-# A variant named l or l_* holds fthe_padic_m37l (--top-est --limb-op) and reads the limb-fed tile image:
+# A variant named l or l_* holds fthe_padic_m37l (--body m37l) and reads the limb-fed tile image:
 #   bash tools/m37_ab.sh TAG s l
 T=${1:?tag}; shift
 N=${M37_LANES:-393216}

@@ -803,13 +803,15 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
     return bad
 
 
-def _m37_asm(gm, variant):
-    """the kernel text of a variant: 'm37' (fthe_padic_m37), 'm37t' (fthe_padic_m37t, the four-tile product 2) or
-    'm37s' (fthe_padic_m37s: m37t with product 1's operand shifted by 8 bytes, 15 tiles) or 'm37l' (fthe_padic_m37l:
-    m37t with product 1 fed the limbs as they lie)"""
-    assert variant in ('m37', 'm37t', 'm37s', 'm37l')
-    return gm.gen_padic_mfma('fthe_padic_' + variant, top_est=variant != 'm37',
-                             q1_shift=gm.Q1_SHIFT if variant == 'm37s' else 0, limb_op=variant == 'm37l')
+def _m37_asm(variant, ab):
+    """the kernel text of a variant (gen_padic_mfma.BODIES: 'm37', 'm37t', the four-tile product 2, 'm37s', m37t with
+    product 1's operand shifted by 8 bytes, or 'm37l', m37t with product 1 fed the limbs as they lie) under the
+    generator switches ab, the generator, and product 1's first column (s1lo112 needs the matching image)"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
+    sys.path.insert(0, here)
+    import gen_padic_mfma as gm
+    return gm.gen_body(variant, ab or ""), gm, gm.s1_lo(ab or "")
 
 
 def _m37_ctx(gm, mm, P, s1_lo, variant):
@@ -832,26 +834,9 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None, ju
     """wave 0 of fthe_padic_m37 (one workgroup of 256 lanes, 4 waves fill the LDS tile image, wave 0 runs on):
     LOADP x; STOREX t; SQR 1; MUL t; STOREP -> x^3 mod P^2 (< 6 P^2), against Python integers on its 64 lanes
     (x < P^2: 0, 1, P - 1, P, P^2 - 1, the values of extra and random).  ab: a generator switch string
-    (FTHE_GEN_M37_AB).  variant: 'm37', 'm37t' or 'm37s'.  P: the modulus (default: random of `bits` bits).
+    (gen_padic_mfma.SWITCHES).  variant: a key of gen_padic_mfma.BODIES.  P: the modulus (default: random of `bits` bits).
     junk_pads: product 1's operand dwords 0, 1 and 37..39 (m37s never writes them) start as random words."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
-    sys.path.insert(0, here)
-    import importlib
-    import gen_padic_mfma as gm
-    saved = os.environ.get("FTHE_GEN_M37_AB")
-    if ab is not None:
-        os.environ["FTHE_GEN_M37_AB"] = ab
-    try:
-        gm = importlib.reload(gm)
-        asm = _m37_asm(gm, variant)
-        s1_lo = gm.S1_LO
-    finally:
-        if saved is None:
-            os.environ.pop("FTHE_GEN_M37_AB", None)
-        else:
-            os.environ["FTHE_GEN_M37_AB"] = saved
-        importlib.reload(gm)
+    asm, gm, s1_lo = _m37_asm(variant, ab)
     import padic_mfma_model as mm
     rng = random.Random(seed)
     if P is None:
@@ -903,24 +888,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
     contract), incl. digits whose low 36 limbs are all 2^28 - 1 (the largest Karatsuba half sums and column
     sums), zero halves, one-limb digits and random ones -- against (x0 + x1 P)^4 mod P^2 in Python integers.
     P: the modulus (default: random of `bits` bits); pairs0: digit pairs that take the first lanes."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
-    sys.path.insert(0, here)
-    import importlib
-    import gen_padic_mfma as gm
-    saved = os.environ.get("FTHE_GEN_M37_AB")
-    if ab is not None:
-        os.environ["FTHE_GEN_M37_AB"] = ab
-    try:
-        gm = importlib.reload(gm)
-        asm = _m37_asm(gm, variant)
-        s1_lo = gm.S1_LO                                          # the s1lo112 switch needs the matching image
-    finally:
-        if saved is None:
-            os.environ.pop("FTHE_GEN_M37_AB", None)
-        else:
-            os.environ["FTHE_GEN_M37_AB"] = saved
-        importlib.reload(gm)
+    asm, gm, s1_lo = _m37_asm(variant, ab)
     import padic_mfma_model as mm
     rng = random.Random(seed)
     if P is None:
