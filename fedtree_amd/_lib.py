@@ -119,6 +119,14 @@ _PROTOS = {
     "fthe_reduce_segments_zero_first_dev": (_I, [_P, _P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "fthe_encode_fixed_dev": (_I, [_P, _P, _SZ, _P]),
     "fthe_decode_fixed_dev": (_I, [_P, _P, _SZ, _P]),
+    "fthe_pack_gh_dev": (_I, [_P, _P, _P, _SZ, _P]),
+    "fthe_unpack_gh_dev": (_I, [_P, _P, _I, _SZ, _P, _P, _P, _P]),
+    "fthe_encrypt_gh_packed_dev": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _U64, _U64, _P, _I]),
+    "fthe_encrypt_gh_packed": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _U64, _U64, _P, _I]),
+    "fthe_decrypt_gh_packed_dev": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P, _I]),
+    "fthe_decrypt_gh_packed": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P, _I]),
+    "fthe_sub_bits_dev": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
+    "fthe_sub_bits": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
     "fthe_last_kernel_ms": (ctypes.c_double, [_P]),
     "fthe_last_montmuls": (ctypes.c_double, [_P]),
     "fthe_kernel_limbs": (_I, [_I]),

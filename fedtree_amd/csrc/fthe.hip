@@ -288,6 +288,8 @@ struct fthe_ctx {
     DevBuf hb[6];                           // histogram CSR / segmented-product plan (device)
     DevBuf ezm;                             // zero-first folds: Enc(0) rows masked to the populated segments
     DevBuf dec[3];                          // decimal codec: 9-digit chunks, lengths, leading chunk / error flag
+    DevBuf gh[3];                           // packed pairs: plaintext words of an encrypt, one decrypt chunk's
+                                            // plaintext words, the host forms' floats / codes
     void *cub_tmp = nullptr; size_t cub_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_mm = 0;
@@ -3142,10 +3144,17 @@ extern "C" int fthe_encrypt_words_dev(fthe_key *k, fthe_ctx *c, const uint32_t *
 
 // ---------------------------------------------------------------------------
 // Decrypt (CRT)
+// Packed gradient pairs (fthe_decrypt_gh_packed): instead of m_low / m_full rows, each chunk's plaintexts go,
+// cut to their low kGhRowWords words, into a chunk-sized context buffer and are decoded from there
+// (k_unpack_gh) into the caller's device arrays (nullable) -- no count x n_words plaintext array.
+struct GhOut { float *g, *h; int64_t *g_code, *h_code; };
+constexpr int kGhRowWords = 8;          // the six packed words, rounded up to the 16-byte stores of mul_add_out
+
 static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, uint64_t *m_low,
-                        uint32_t *m_full, HostPipe *pipe, bool short_pt = false) {
+                        uint32_t *m_full, HostPipe *pipe, bool short_pt = false, const GhOut *gh = nullptr) {
     if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
     if (!k->priv) return FTHE_ERR_NOPRIV;
+    if (gh && (m_low || m_full || k->n_words < FTHE_GH_PACKED_WORDS)) return FTHE_ERR_ARG;
     // Batches that leave most of the chip idle (a GHPair from decrypt_gh, one tree node's sums) run the
     // c^(q-1) mod q^2 exponentiation beside c^(p-1) mod p^2, or both on the four-lane kernel (plan_call);
     // either way c^(P-1) mod P^2 ends in the s74 slots of the unchanged L-function / CRT tail.
@@ -3157,6 +3166,18 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
     const bool quad = pl.quad, split = pl.split;
     Launch &Lc = pl.main, &Lq = pl.q, &Lp4 = pl.p4, &Lq4 = pl.q4;
     const int S = Lc.S, L = Lc.L, nw = k->n_words, cw = 2 * nw;
+    if (gh && (rc = c->gh[1].ensure((size_t)L * kGhRowWords * 4))) return rc;
+    // where chunk [off, off + cnt) leaves its plaintext rows, and their width in words
+    const int mw = gh ? kGhRowWords : nw;
+    auto m_rows = [&](size_t off) {
+        return gh ? (uint32_t *)c->gh[1].p : m_full ? m_full + off * nw : (uint32_t *)nullptr;
+    };
+    auto gh_decode = [&](size_t off, size_t cnt) {
+        if (gh)
+            hipLaunchKernelGGL(k_unpack_gh, Lc.grid(), dim3(256), 0, c->stream, (const uint32_t *)c->gh[1].p,
+                               kGhRowWords, cnt, gh->g ? gh->g + off : nullptr, gh->h ? gh->h + off : nullptr,
+                               gh->g_code ? gh->g_code + off : nullptr, gh->h_code ? gh->h_code + off : nullptr);
+    };
     if (quad) {
         fill_dec_consts(Lp4, kHalfP, true);
         if (!short_pt) fill_dec_consts(Lq4, kHalfQ, true);
@@ -3212,8 +3233,8 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
             hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTP), k->cst(k->c_p), S, L, Lc.B);
             hipLaunchKernelGGL(k_mul_add_out, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_OUTP), k->kp,
                                k->cst(k->c_zero), 1, Lc.slot(SL_OUTP), k->kp, L, cnt,
-                               m_full ? m_full + off * nw : (uint32_t *)nullptr, nw,
-                               m_low ? m_low + off : (uint64_t *)nullptr, Lc.B);
+                               m_rows(off), mw, m_low ? m_low + off : (uint64_t *)nullptr, Lc.B);
+            gh_decode(off, cnt);
             if (off + L < count) Lc.fill(SL_C0, k->c_R2p);
             if (pipe && (rc = pipe->after(off, cnt))) return rc;
             continue;
@@ -3237,8 +3258,8 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
         hipLaunchKernelGGL(k_canon, Lc.grid(), dim3(256), 0, c->stream, Lc.slot(SL_T4), k->cst(k->c_p), S, L, Lc.B);
         // m = mq + q t   (< n)
         mul_add_out(c->stream, Lc.grid(), Lc.slot(SL_OUTQ), S, k->cst(k->c_q), k->kq, Lc.slot(SL_T4), k->kp, L, cnt,
-                    m_full ? m_full + off * nw : (uint32_t *)nullptr, nw, m_low ? m_low + off : (uint64_t *)nullptr,
-                    Lc.B);
+                    m_rows(off), mw, m_low ? m_low + off : (uint64_t *)nullptr, Lc.B);
+        gh_decode(off, cnt);
         if (off + L < count) {   // restore the exponentiation constants for the next chunk
             Lc.fill(SL_C0, k->c_R2p); Lc.fill(SL_C1, k->c_R3p); Lc.fill(SL_C2, k->c_R2q);
         }
@@ -3256,6 +3277,54 @@ extern "C" int fthe_decrypt_dev(fthe_key *k, fthe_ctx *c, const uint32_t *ct, si
 extern "C" int fthe_decrypt_short_dev(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count,
                                       uint64_t *m_low, uint32_t *m_full) {
     return decrypt_impl(k, c, ct, count, m_low, m_full, nullptr, true);
+}
+
+// ---------------------------------------------------------------------------
+// Packed gradient pairs: one ciphertext per (g, h) (include/fthe.h)
+static dim3 grid256(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
+
+extern "C" int fthe_pack_gh_dev(fthe_ctx *c, const float *g, const float *h, size_t count, uint32_t *m) {
+    if (!c || ((!g || !h || !m) && count)) return FTHE_ERR_ARG;
+    if (!count) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_pack_gh, grid256(count), dim3(256), 0, c->stream, g, h, count, m);
+    return hipGetLastError() == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+}
+
+extern "C" int fthe_unpack_gh_dev(fthe_ctx *c, const uint32_t *m, int stride_words, size_t count, float *g, float *h,
+                                  int64_t *g_code, int64_t *h_code) {
+    if (!c || (!m && count) || stride_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
+    if (!count) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_unpack_gh, grid256(count), dim3(256), 0, c->stream, m, stride_words, count, g, h, g_code,
+                       h_code);
+    return hipGetLastError() == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+}
+
+// (g, h) device floats -> the packed plaintext words in the context's buffer -> the encrypt of general
+// plaintexts (MsgSrc::mw): every flag and randomness form of fthe_encrypt_u64_at applies as it is.
+static int encrypt_gh_impl(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count, const uint32_t *r,
+                           int r_words, uint64_t rng_seed, uint64_t index0, uint32_t *out, int flags, HostPipe *pipe) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    int rc = c->gh[0].ensure(std::max<size_t>(4, count * FTHE_GH_PACKED_WORDS * 4));
+    if (rc) return rc;
+    if (count) hipLaunchKernelGGL(k_pack_gh, grid256(count), dim3(256), 0, c->stream, g, h, count, (uint32_t *)c->gh[0].p);
+    MsgSrc ms; ms.mw = (const uint32_t *)c->gh[0].p; ms.mww = FTHE_GH_PACKED_WORDS; ms.idx0 = index0;
+    return encrypt_impl(k, c, ms, count, r, r_words, rng_seed, out, flags, pipe);
+}
+
+extern "C" int fthe_encrypt_gh_packed_dev(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                          const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
+                                          uint32_t *out, int flags) {
+    return encrypt_gh_impl(k, c, g, h, count, r, r_words, rng_seed, index0, out, flags, nullptr);
+}
+
+extern "C" int fthe_decrypt_gh_packed_dev(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, float *g,
+                                          float *h, int64_t *g_code, int64_t *h_code, int short_pt) {
+    const GhOut o{g, h, g_code, h_code};
+    return decrypt_impl(k, c, ct, count, nullptr, nullptr, nullptr, short_pt != 0, &o);
 }
 
 // ---------------------------------------------------------------------------
@@ -3356,17 +3425,37 @@ extern "C" int fthe_debug_nadicb_image(const uint32_t *n, int n_words, uint8_t *
     return FTHE_OK;
 }
 
+// sub_bits: 0 = the add; else out = a * b^(2^sub_bits - 1) mod n^2 -- 64: GHPair::operator- on the key's own
+// programs (fthe_sub); any other width (fthe_sub_bits): the same program with that all-ones chain, built for
+// the call.
 static int pair_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out,
-                     HostPipe *pipe, bool sub) {
+                     HostPipe *pipe, int sub_bits) {
     if (!k || !c || ((!a || !b || !out) && count)) return FTHE_ERR_ARG;
     if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    const bool sub = sub_bits != 0, dyn = sub && sub_bits != 64;
+    if (sub && (sub_bits < 8 || sub_bits > 32 * k->n_words)) return FTHE_ERR_ARG;
     Launch Lc;
-    // Row I/O reads and writes the AoS rows directly: the only slot is the R^2 constant, so
-    // device-resident calls take 4x larger launches (fewer launch tails) at no memory cost.
-    int rc = k->rowio ? begin_call(c, k, count, Lc, SL_C0 + 1, k->sn2, pipe ? 0 : rowio_chunk_lanes())
+    // Row I/O reads and writes the AoS rows directly: the only slot of an add is the R^2 constant, so
+    // device-resident calls take 4x larger launches (fewer launch tails) at no memory cost.  A sub also
+    // keeps its all-ones chain's base and temporary in slots T0 / T1.
+    int rc = k->rowio ? begin_call(c, k, count, Lc, sub ? SL_T1 + 1 : SL_C0 + 1, k->sn2, pipe ? 0 : rowio_chunk_lanes())
                       : begin_call(c, k, count, Lc, nslots_for(k), k->sn2);
     if (rc) return rc;
     const int S = Lc.S, L = Lc.L, cw = 2 * k->n_words;
+    Prog dp;
+    if (dyn) {
+        if (k->rowio) {
+            dp.loadw(1); dp.mul(SL_C0); dp.pow_ones((unsigned)sub_bits, SL_T0, SL_T1); dp.mulw(0); dp.storew(2);
+        } else {
+            dp.lds_a = lds_prefetch(k->sn2);
+            dp.loadx(SL_IN1); dp.mul(SL_C0); dp.pow_ones((unsigned)sub_bits, SL_T0, SL_T1); dp.mul(SL_IN0);
+            dp.storex(SL_OUTP);
+        }
+        dp.end();
+        fthe_key::PH ph;
+        if ((rc = upload_dyn_prog(c, dp, ph, c->io[3]))) return rc;
+        HIPOK(hipEventRecord(c->ev0, c->stream));      // fthe_last_kernel_ms: not the upload's drain
+    }
     const bool addb = !sub && k->d_addb && c->fn_addb;
     if (addb && !pipe) {
         // device rows: one launch of persistent workgroups for the whole batch (no chunk tails)
@@ -3384,11 +3473,13 @@ static int pair_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t
             Lc.mm += (double)cnt;
         } else if (k->rowio) {
             const void *rows[3] = {a + off * cw, b + off * cw, out + off * cw};
-            if ((rc = Lc.prog(sub ? k->pr_sub_w : k->pr_add_w, k->mn2, rows, 3))) return rc;
+            if ((rc = dyn ? launch_dyn(Lc, c->io[3].p, dp.montmuls, k->mn2, rows, 3)
+                          : Lc.prog(sub ? k->pr_sub_w : k->pr_add_w, k->mn2, rows, 3))) return rc;
         } else {
             pack_rows(c->stream, a + off * cw, cw, cnt, 0, Lc.slot(SL_IN0), S, L, Lc.B);
             pack_rows(c->stream, b + off * cw, cw, cnt, 0, Lc.slot(SL_IN1), S, L, Lc.B);
-            if ((rc = Lc.prog(sub ? k->pr_sub : k->pr_add, k->mn2))) return rc;
+            if ((rc = dyn ? launch_dyn(Lc, c->io[3].p, dp.montmuls, k->mn2)
+                          : Lc.prog(sub ? k->pr_sub : k->pr_add, k->mn2))) return rc;
             unpack_rows(c->stream, Lc.slot(SL_OUTP), k->cst(k->c_n2), S, L,
                                cnt, out + off * cw, cw, Lc.B);
         }
@@ -3398,13 +3489,21 @@ static int pair_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t
 }
 
 extern "C" int fthe_add_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out) {
-    return pair_impl(k, c, a, b, count, out, nullptr, false);
+    return pair_impl(k, c, a, b, count, out, nullptr, 0);
 }
 
 // out = a * b^(2^64-1) mod n^2: the homomorphic a - b of GHPair::operator- (common.h:253-337,
 // both operands encrypted), i.e. Paillier::add(a, Paillier::mul(b, (unsigned long)-1)).
 extern "C" int fthe_sub_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out) {
-    return pair_impl(k, c, a, b, count, out, nullptr, true);
+    return pair_impl(k, c, a, b, count, out, nullptr, 64);
+}
+
+// out = a * b^(2^bits - 1) mod n^2: the homomorphic a - b on plaintexts that live mod 2^bits (packed gradient
+// pairs: bits = FTHE_GH_PACKED_BITS); bits = 64 is fthe_sub_dev.
+extern "C" int fthe_sub_bits_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, int bits,
+                                 uint32_t *out) {
+    if (bits <= 0) return FTHE_ERR_ARG;
+    return pair_impl(k, c, a, b, count, out, nullptr, bits);
 }
 
 // Programs built per call (k-way product, scalar exponent) go through a
@@ -4059,6 +4158,59 @@ extern "C" int fthe_decrypt(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t
     return decrypt_host(k, c, ct, count, m_low, m_full, false);
 }
 
+// Host-resident packed pairs.  The floats and codes are 8 to 24 bytes per pair beside 8 n_words of
+// ciphertext: they cross in one copy each, and only the ciphertext rows (and injected r) go through the pipe.
+extern "C" int fthe_encrypt_gh_packed(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                      const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
+                                      uint32_t *out, int flags) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
+    if (r && (r_words <= 0 || r_words > ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
+                                         : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)))) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t cw = 2 * (size_t)k->n_words;
+    int rc;
+    if ((rc = c->gh[2].ensure(std::max<size_t>(4, count * 8))) || (rc = c->io[2].ensure(std::max<size_t>(4, count * cw * 4))))
+        return rc;
+    if (r && (rc = c->io[1].ensure(std::max<size_t>(4, count * r_words * 4)))) return rc;
+    float *dg = (float *)c->gh[2].p, *dh = dg + count;
+    if (count) {
+        HIPOK(hipMemcpyAsync(dg, g, count * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(dh, h, count * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HostPipe pipe{c};
+    if (r) pipe.add_in(r, c->io[1].p, (size_t)r_words * 4);
+    pipe.add_out(out, c->io[2].p, cw * 4);
+    if ((rc = encrypt_gh_impl(k, c, dg, dh, count, r ? (const uint32_t *)c->io[1].p : nullptr, r_words, rng_seed,
+                              index0, (uint32_t *)c->io[2].p, flags, count ? &pipe : nullptr))) return rc;
+    return pipe.finish();
+}
+
+extern "C" int fthe_decrypt_gh_packed(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, float *g, float *h,
+                                      int64_t *g_code, int64_t *h_code, int short_pt) {
+    if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t cw = 2 * (size_t)k->n_words;
+    int rc;
+    // device outputs in one buffer: g codes, h codes, g floats, h floats
+    if ((rc = c->io[0].ensure(std::max<size_t>(4, count * cw * 4))) || (rc = c->gh[2].ensure(std::max<size_t>(8, count * 24))))
+        return rc;
+    int64_t *dgc = (int64_t *)c->gh[2].p, *dhc = dgc + count;
+    float *dg = (float *)(dhc + count), *dh = dg + count;
+    const GhOut o{dg, dh, dgc, dhc};
+    HostPipe pipe{c};
+    pipe.add_in(ct, c->io[0].p, cw * 4);
+    if ((rc = decrypt_impl(k, c, (const uint32_t *)c->io[0].p, count, nullptr, nullptr, count ? &pipe : nullptr,
+                           short_pt != 0, &o))) return rc;
+    if ((rc = pipe.finish())) return rc;
+    if (!count) return FTHE_OK;
+    if (g) HIPOK(hipMemcpy(g, dg, count * 4, hipMemcpyDeviceToHost));
+    if (h) HIPOK(hipMemcpy(h, dh, count * 4, hipMemcpyDeviceToHost));
+    if (g_code) HIPOK(hipMemcpy(g_code, dgc, count * 8, hipMemcpyDeviceToHost));
+    if (h_code) HIPOK(hipMemcpy(h_code, dhc, count * 8, hipMemcpyDeviceToHost));
+    return FTHE_OK;
+}
+
 // Staging buffers of the shared queues above this many bytes are released after their batch
 // (one large shared call must not pin a second copy of its ciphertexts for the key's lifetime).
 constexpr size_t kCoalesceKeepBytes = (size_t)64 << 20;
@@ -4253,7 +4405,7 @@ static size_t small_host_rows() {
     return v;
 }
 static int pair_host(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out,
-                     bool sub) {
+                     int sub) {                  // pair_impl's sub_bits
     if (!k || !c || ((!a || !b || !out) && count)) return FTHE_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     size_t row = 2 * (size_t)k->n_words * 4;
@@ -4281,11 +4433,17 @@ static int pair_host(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t
 }
 
 extern "C" int fthe_add(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out) {
-    return pair_host(k, c, a, b, count, out, false);
+    return pair_host(k, c, a, b, count, out, 0);
 }
 
 extern "C" int fthe_sub(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out) {
-    return pair_host(k, c, a, b, count, out, true);
+    return pair_host(k, c, a, b, count, out, 64);
+}
+
+extern "C" int fthe_sub_bits(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, int bits,
+                             uint32_t *out) {
+    if (bits <= 0) return FTHE_ERR_ARG;
+    return pair_host(k, c, a, b, count, out, bits);
 }
 
 extern "C" int fthe_reduce_kway(fthe_key *k, fthe_ctx *c, const uint32_t *x, int kk, size_t count, uint32_t *out) {

@@ -55,4 +55,8 @@ int dec_launch_parse(const char *buf, const int64_t *off, size_t count, int word
                      hipStream_t st);
 __global__ void k_encode_fixed(const float *x, size_t count, uint64_t *m);
 __global__ void k_decode_fixed(const uint64_t *m, size_t count, float *x);
+// packed gradient pairs: one 192-bit plaintext per (g, h) (include/fthe.h FTHE_GH_*)
+__global__ void k_pack_gh(const float *g, const float *h, size_t count, uint32_t *m);
+__global__ void k_unpack_gh(const uint32_t *m, int stride, size_t count, float *g, float *h, int64_t *g_code,
+                            int64_t *h_code);
 }  // namespace fthe

@@ -55,6 +55,78 @@ def decode_fixed(m):
 
 
 # --------------------------------------------------------------------------
+# Packed gradient pairs (include/fthe.h FTHE_GH_*): both codes of a pair in one
+# plaintext, M = code(g) + code(h) 2^S mod 2^W.  These numpy functions are the executable statement
+# of the layout; the engine's k_pack_gh / k_unpack_gh are checked against them.
+GH_FIELD_BITS = 96
+GH_PACKED_BITS = 192
+GH_PACKED_WORDS = 6
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def pack_codes(g_code, h_code):
+    """int64 codes -> (count, 6) uint32 words of (g_code + h_code 2^96) mod 2^192: g_code is sign-extended
+    through the whole number (a negative g borrows from the h field)."""
+    cg = np.ascontiguousarray(g_code, dtype=np.int64).reshape(-1)
+    ch = np.ascontiguousarray(h_code, dtype=np.int64).reshape(-1)
+    ug, uh = cg.view(np.uint64), ch.view(np.uint64)
+    sg = np.where(cg < 0, _M32, np.uint64(0)).astype(np.uint64)
+    sh = np.where(ch < 0, _M32, np.uint64(0)).astype(np.uint64)
+    out = np.zeros((len(cg), GH_PACKED_WORDS), dtype=np.uint32)
+    out[:, 0] = (ug & _M32).astype(np.uint32)
+    out[:, 1] = (ug >> _S32).astype(np.uint32)
+    out[:, 2] = sg.astype(np.uint32)
+    s = sg + (uh & _M32)
+    out[:, 3] = (s & _M32).astype(np.uint32)
+    s = (s >> _S32) + sg + (uh >> _S32)
+    out[:, 4] = (s & _M32).astype(np.uint32)
+    s = (s >> _S32) + sg + sh
+    out[:, 5] = (s & _M32).astype(np.uint32)
+    return out
+
+
+def pack_gh(g, h):
+    """float g, h -> the packed plaintext words, (count, 6) uint32."""
+    return pack_codes(encode_fixed(g).view(np.int64), encode_fixed(h).view(np.int64))
+
+
+def unpack_codes(words):
+    """Low six words of each plaintext row (a sum or difference of packed plaintexts) -> the int64 codes
+    (g_code, h_code): the signed low 96 bits, and what is left above them once they are taken out, each
+    cut to its low 64 bits -- the codes the two-ciphertext flow decrypts."""
+    w = np.asarray(words, dtype=np.uint32)
+    w = w.reshape(-1, w.shape[-1])[:, :GH_PACKED_WORDS].astype(np.uint64)
+    cg = w[:, 0] | (w[:, 1] << _S32)
+    ch = (w[:, 3] | (w[:, 4] << _S32)) + (w[:, 2] >> np.uint64(31))        # wraps mod 2^64
+    return cg.view(np.int64), ch.view(np.int64)
+
+
+def unpack_gh(words, codes=False):
+    """Plaintext rows -> float (g, h) as GHPair::homo_decrypt decodes them; codes: also the int64 codes."""
+    cg, ch = unpack_codes(words)
+    g, h = decode_fixed(cg.view(np.uint64)), decode_fixed(ch.view(np.uint64))
+    return (g, h, cg, ch) if codes else (g, h)
+
+
+def packed_bits_after(op, bits_a, bits_b=None, k=None):
+    """Upper bound on the bits of a packed plaintext after an operation (the growth rule):
+      "add": a + b                           -> max(bits_a, bits_b) + 1
+      "sub": a - b = a + b (2^192 - 1)       -> max(bits_a, bits_b + 192) + 1
+      "sum": k addends of at most bits_a bits (segment products, histogram bins, prefix scans)
+                                             -> bits_a + ceil(log2 k)
+    A fresh packed plaintext has 192 bits (a negative code fills the top field).  A result decrypts
+    correctly only while its bound stays below the bits of n (of p for the short decrypt)."""
+    if op == "add":
+        return max(int(bits_a), int(bits_b)) + 1
+    if op == "sub":
+        return max(int(bits_a), int(bits_b) + GH_PACKED_BITS) + 1
+    if op == "sum":
+        return int(bits_a) + max(0, int(k) - 1).bit_length()
+    raise ValueError(f"packed_bits_after: unknown op {op!r}")
+
+
+# --------------------------------------------------------------------------
 class Device:
     """One engine context (HIP stream + workspace) on one GPU.
 
@@ -333,6 +405,15 @@ class Paillier:
         m = np.ascontiguousarray(m, dtype=np.uint64).reshape(-1)
         cnt = len(m)
         out = np.zeros((cnt, self._cw()), dtype=np.uint32)
+        rw = self._rand_rows(r, cnt, public, fixed_base, fixed_base_exact)
+        flags = self._flags(public, fixed_base, fixed_base_exact)
+        _lib.check(self.lib.fthe_encrypt_u64_at(self._key, self.dev.ctx, _ptr(m), cnt, _ptr(rw),
+                                                rw.shape[1] if rw is not None else 0, int(seed), int(index0),
+                                                _ptr(out), flags), "encrypt")
+        return out
+
+    def _rand_rows(self, r, cnt, public, fixed_base, fixed_base_exact):
+        """Injected randomness of an encrypt call (see encrypt_u64) as (cnt, words) uint32 rows, or None."""
         rw = None
         if r is not None:
             if not isinstance(r, np.ndarray) and fixed_base_exact:
@@ -348,10 +429,48 @@ class Paillier:
                     nw = max(1, max((int(x).bit_length() + 31) // 32 for x in r))
                 r = np.stack([_words(int(x), nw) for x in r]) if cnt else np.zeros((0, nw), np.uint32)
             rw = np.ascontiguousarray(r, dtype=np.uint32).reshape(cnt, -1)
-        flags = self._flags(public, fixed_base, fixed_base_exact)
-        _lib.check(self.lib.fthe_encrypt_u64_at(self._key, self.dev.ctx, _ptr(m), cnt, _ptr(rw),
-                                                rw.shape[1] if rw is not None else 0, int(seed), int(index0),
-                                                _ptr(out), flags), "encrypt")
+        return rw
+
+    # ---- packed gradient pairs: one ciphertext per (g, h) (include/fthe.h FTHE_GH_*) ----------
+    def encrypt_gh_packed(self, g, h, r=None, seed=0, public=False, fixed_base=False, fixed_base_exact=False,
+                          index0=0):
+        """Enc(pack_gh(g, h)): one ciphertext per pair (fthe_encrypt_gh_packed); r, seed, index0 and the
+        modes as encrypt_u64.  Keys of fewer than six words are rejected."""
+        g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        if len(g) != len(h):
+            raise ValueError(f"encrypt_gh_packed: {len(g)} g for {len(h)} h")
+        cnt = len(g)
+        out = np.zeros((cnt, self._cw()), dtype=np.uint32)
+        rw = self._rand_rows(r, cnt, public, fixed_base, fixed_base_exact)
+        _lib.check(self.lib.fthe_encrypt_gh_packed(self._key, self.dev.ctx, _ptr(g), _ptr(h), cnt, _ptr(rw),
+                                                   rw.shape[1] if rw is not None else 0, int(seed), int(index0),
+                                                   _ptr(out), self._flags(public, fixed_base, fixed_base_exact)),
+                   "encrypt_gh_packed")
+        return out
+
+    def decrypt_gh_packed(self, c, short=False, codes=False):
+        """Packed ciphertexts -> float (g, h) (codes: also the int64 codes), decoded on the device chunk by
+        chunk (fthe_decrypt_gh_packed).  short: plaintexts known < p (fthe_decrypt_short semantics)."""
+        c = np.ascontiguousarray(c, dtype=np.uint32).reshape(-1, self._cw())
+        cnt = len(c)
+        g, h = np.zeros(cnt, np.float32), np.zeros(cnt, np.float32)
+        gc = np.zeros(cnt, np.int64) if codes else None
+        hc = np.zeros(cnt, np.int64) if codes else None
+        _lib.check(self.lib.fthe_decrypt_gh_packed(self._key, self.dev.ctx, _ptr(c), cnt, _ptr(g), _ptr(h), _ptr(gc),
+                                                   _ptr(hc), int(bool(short))), "decrypt_gh_packed")
+        return (g, h, gc, hc) if codes else (g, h)
+
+    def sub_bits_batch(self, a, b, bits=GH_PACKED_BITS):
+        """a * b^(2^bits - 1) mod n^2 (fthe_sub_bits): a - b on plaintexts that live mod 2^bits; the
+        default is the packed pairs' width, bits = 64 is sub_batch."""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, self._cw())
+        b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, self._cw())
+        if b.shape != a.shape:
+            raise ValueError(f"sub_bits_batch: operand shapes differ ({a.shape} vs {b.shape})")
+        out = np.zeros_like(a)
+        _lib.check(self.lib.fthe_sub_bits(self._key, self.dev.ctx, _ptr(a), _ptr(b), len(a), int(bits), _ptr(out)),
+                   "sub_bits")
         return out
 
     def direct_y(self, seed, index0, count):
@@ -533,6 +652,49 @@ class Paillier:
         return out
 
     @_stream_ordered
+    def sub_bits_dev(self, a, b, out, bits=GH_PACKED_BITS):
+        cnt = a.numel() // self._cw()
+        _lib.check(self.lib.fthe_sub_bits_dev(self._key, self.dev.ctx, ctypes.c_void_p(a.data_ptr()),
+                                              ctypes.c_void_p(b.data_ptr()), cnt, int(bits),
+                                              ctypes.c_void_p(out.data_ptr())), "sub_bits_dev")
+        return out
+
+    @_stream_ordered
+    def pack_gh_dev(self, g, h, out):
+        """Device float32 g, h -> device (count, 6) packed plaintext words (fthe_pack_gh_dev)."""
+        _lib.check(self.lib.fthe_pack_gh_dev(self.dev.ctx, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(h.data_ptr()),
+                                             g.numel(), ctypes.c_void_p(out.data_ptr())), "pack_gh_dev")
+        return out
+
+    @staticmethod
+    def _dptr(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    @_stream_ordered
+    def unpack_gh_dev(self, m, count, g=None, h=None, g_code=None, h_code=None, stride_words=GH_PACKED_WORDS):
+        """Device plaintext rows stride_words apart -> device float32 g, h and int64 codes (each optional)."""
+        _lib.check(self.lib.fthe_unpack_gh_dev(self.dev.ctx, ctypes.c_void_p(m.data_ptr()), int(stride_words),
+                                               int(count), self._dptr(g), self._dptr(h), self._dptr(g_code),
+                                               self._dptr(h_code)), "unpack_gh_dev")
+
+    @_stream_ordered
+    def encrypt_gh_packed_dev(self, g, h, out, r=None, seed=0, public=False, fixed_base=False,
+                              fixed_base_exact=False, index0=0):
+        """Device float32 g, h -> device packed ciphertexts out (count, 2nw); otherwise as encrypt_u64_dev."""
+        _lib.check(self.lib.fthe_encrypt_gh_packed_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(h.data_ptr()), g.numel(),
+            self._dptr(r), r.shape[-1] if r is not None else 0, int(seed), int(index0),
+            ctypes.c_void_p(out.data_ptr()), self._flags(public, fixed_base, fixed_base_exact)), "encrypt_gh_packed_dev")
+        return out
+
+    @_stream_ordered
+    def decrypt_gh_packed_dev(self, c, g=None, h=None, g_code=None, h_code=None, short=False):
+        """Device packed ciphertexts -> device float32 g, h and int64 codes (each optional)."""
+        _lib.check(self.lib.fthe_decrypt_gh_packed_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(c.data_ptr()), c.numel() // self._cw(), self._dptr(g),
+            self._dptr(h), self._dptr(g_code), self._dptr(h_code), int(bool(short))), "decrypt_gh_packed_dev")
+
+    @_stream_ordered
     def scan_segments_dev(self, x, seg_ptr, out):
         seg = np.ascontiguousarray(seg_ptr, dtype=np.int64)
         _lib.check(self.lib.fthe_scan_segments_dev(self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()), _ptr(seg),
@@ -661,14 +823,20 @@ class Paillier:
 class GHPairs:
     """A batch of GHPair (common.h:65-412): float g, h plus ciphertexts g_enc,
     h_enc and the `encrypted` flag.  Arrays are numpy; ciphertexts are
-    (count, 2*n_words) uint32."""
+    (count, 2*n_words) uint32.
 
-    def __init__(self, g, h=None, paillier=None):
+    packed=True (opt-in, include/fthe.h FTHE_GH_*): one ciphertext per pair -- g_enc holds the packed
+    ciphertexts and h_enc is None.  pt_bits is then an upper bound on the bits of the plaintexts
+    (packed_bits_after), checked against the key before a decrypt."""
+
+    def __init__(self, g, h=None, paillier=None, packed=False):
         self.g = np.ascontiguousarray(g, dtype=np.float32).copy()
         self.h = np.ascontiguousarray(h if h is not None else g, dtype=np.float32).copy()
         self.encrypted = False
         self.g_enc = self.h_enc = None
         self.paillier = paillier
+        self.packed = bool(packed)
+        self.pt_bits = 0
 
     def __len__(self):
         return len(self.g)
@@ -678,6 +846,16 @@ class GHPairs:
         fixed_base_exact: the table-driven randomizer (key holder: same distribution; public
         key with published bases: within 2^-62 of it; otherwise the default path)."""
         if self.encrypted:
+            return self
+        if self.packed:
+            fbx = fixed_base_exact and r_g is None and (pl.has_private or pl.has_public_bases)
+            self.g_enc = pl.encrypt_gh_packed(self.g, self.h, r=r_g, seed=seed, fixed_base_exact=fbx)
+            self.h_enc = None
+            self.pt_bits = GH_PACKED_BITS
+            self.paillier = pl
+            self.g[:] = 0
+            self.h[:] = 0
+            self.encrypted = True
             return self
         m = np.concatenate([encode_fixed(self.g), encode_fixed(self.h)])
         r = None
@@ -696,8 +874,19 @@ class GHPairs:
     def homo_decrypt(self, pl, short=False, shared=False):
         """GHPair::homo_decrypt (common.h:136-146): g = (float)(long)dec / 1e6.
         short: plaintexts known < p (codec values and their sums): p half of the CRT only.
-        shared: through the key's coalescing queue (thread-safe on one key, fthe_decrypt_shared)."""
+        shared: through the key's coalescing queue (thread-safe on one key, fthe_decrypt_shared).
+        Packed pairs take the packed decrypt on the caller's context (shared has no packed form) and
+        raise ValueError, before any device work, when pt_bits does not fit below n (p for short)."""
         if not self.encrypted:
+            return self
+        if self.packed:
+            # the one limit of the packed mode: a plaintext that outgrew the key would decode to wrong floats
+            room = pl.p.bit_length() if short else pl.modulus.bit_length()
+            if self.pt_bits >= room:
+                raise ValueError(f"packed plaintexts of up to {self.pt_bits} bits do not fit below "
+                                 f"{'p' if short else 'n'} ({room} bits): pt_bits must stay under it")
+            self.g, self.h = pl.decrypt_gh_packed(self.g_enc, short=short)
+            self.encrypted = False
             return self
         dec = pl.decrypt_u64_shared if shared else pl.decrypt_u64
         low = dec(np.concatenate([self.g_enc, self.h_enc]), short=short)
@@ -706,9 +895,20 @@ class GHPairs:
         self.encrypted = False
         return self
 
-    def _enc_side(self, pl):
-        t = GHPairs(self.g, self.h)
+    def _enc_side(self, pl, packed=False):
+        t = GHPairs(self.g, self.h, packed=packed)
         return t.homo_encrypt(pl)
+
+    def _mode_with(self, rhs):
+        """packed flag of an operation's result: that of its encrypted operand(s), which must agree."""
+        if self.encrypted and rhs.encrypted and self.packed != rhs.packed:
+            raise ValueError("GHPairs: one operand is packed (one ciphertext per pair), the other is not")
+        return self.packed if self.encrypted else rhs.packed
+
+    def _packed_result(self, pl, rows, pt_bits):
+        res = GHPairs(np.zeros(len(rows), np.float32), np.zeros(len(rows), np.float32), pl, packed=True)
+        res.g_enc, res.pt_bits, res.encrypted = rows, pt_bits, True
+        return res
 
     def __add__(self, rhs):
         """GHPair::operator+ (common.h:150-195).  An unencrypted side is first
@@ -716,8 +916,12 @@ class GHPairs:
         if not self.encrypted and not rhs.encrypted:
             return GHPairs(self.g + rhs.g, self.h + rhs.h)
         pl = rhs.paillier if not self.encrypted else self.paillier
-        lhs = self if self.encrypted else self._enc_side(pl)
-        r = rhs if rhs.encrypted else rhs._enc_side(pl)
+        packed = self._mode_with(rhs)
+        lhs = self if self.encrypted else self._enc_side(pl, packed)
+        r = rhs if rhs.encrypted else rhs._enc_side(pl, packed)
+        if packed:
+            return self._packed_result(pl, pl.add_batch(lhs.g_enc, r.g_enc),
+                                       packed_bits_after("add", lhs.pt_bits, r.pt_bits))
         res = GHPairs(np.zeros(len(self), np.float32), np.zeros(len(self), np.float32), pl)
         both = pl.add_batch(np.concatenate([lhs.g_enc, lhs.h_enc]), np.concatenate([r.g_enc, r.h_enc]))
         res.g_enc, res.h_enc = both[:len(self)], both[len(self):]
@@ -731,9 +935,13 @@ class GHPairs:
             return GHPairs(self.g - rhs.g, self.h - rhs.h)
         if not rhs.encrypted:
             neg = GHPairs(-rhs.g, -rhs.h)
-            return self + neg._enc_side(self.paillier)
+            return self + neg._enc_side(self.paillier, self.packed)
         pl = rhs.paillier if not self.encrypted else self.paillier
-        lhs = self if self.encrypted else self._enc_side(pl)
+        packed = self._mode_with(rhs)
+        lhs = self if self.encrypted else self._enc_side(pl, packed)
+        if packed:          # exponent 2^192 - 1: 2^64 - 1 would leave m_b 2^64 inside the h field
+            return self._packed_result(pl, pl.sub_bits_batch(lhs.g_enc, rhs.g_enc, GH_PACKED_BITS),
+                                       packed_bits_after("sub", lhs.pt_bits, rhs.pt_bits))
         both = pl.sub_batch(np.concatenate([lhs.g_enc, lhs.h_enc]), np.concatenate([rhs.g_enc, rhs.h_enc]))
         res = GHPairs(np.zeros(len(rhs), np.float32), np.zeros(len(rhs), np.float32), pl)
         res.g_enc, res.h_enc = both[:len(rhs)], both[len(rhs):]
@@ -782,19 +990,23 @@ class HEServer:
             self._bases = self.paillier.public_bases()
         party.paillier = self.paillier.public(self._bases if bases else None)
 
-    def encrypt_gh_pairs(self, raw, seed=0, fixed_base_exact=False):
-        """server.h:113-135."""
+    def encrypt_gh_pairs(self, raw, seed=0, fixed_base_exact=False, packed=None):
+        """server.h:113-135.  packed=True: one ciphertext per pair (GHPairs packed mode, opt-in)."""
+        if packed is not None and not raw.encrypted:
+            raw.packed = bool(packed)
         return raw.homo_encrypt(self.paillier, seed=seed, fixed_base_exact=fixed_base_exact)
 
     def decrypt_gh_pairs(self, encrypted, short=False):
-        """server.h:80-111.  short: see GHPairs.homo_decrypt (opt-in, ~2x)."""
+        """server.h:80-111.  short: see GHPairs.homo_decrypt (opt-in, ~2x).  Packed pairs take the
+        packed decrypt and raise when their pt_bits does not fit the key."""
         return encrypted.homo_decrypt(self.paillier, short=short)
 
     def decrypt_gh(self, gh):
         """server.h:69-78 (single pair).  FedTree calls it per tree node from OpenMP threads
         (FLtrainer.cpp:758-764): it goes through the key's coalescing queue, so concurrent
-        calls share one launch and threads need no context of their own."""
-        return gh.homo_decrypt(self.paillier, shared=True)
+        calls share one launch and threads need no context of their own.  (Packed pairs: the plain
+        packed decrypt on the caller's context.)"""
+        return gh.homo_decrypt(self.paillier, shared=not gh.packed)
 
 
 class HEParty:
@@ -816,7 +1028,8 @@ class HEParty:
         populated bin is the product of its members (the reference's first add
         also folds in a fresh Enc(0) from promoting the zero accumulator,
         common.h:156-160 -- same plaintext, different randomness).
-        Plain gh: float32 accumulation in instance order (dest.g += src.g)."""
+        Plain gh: float32 accumulation in instance order (dest.g += src.g).
+        Packed gh: the same product over one plane; an empty bin, the ciphertext 1, decodes to (0, 0)."""
         seg_ptr, idx = histogram_segments(bin_ids, cut_col_ptr, max_num_bin)
         n_bins = len(seg_ptr) - 1
         if not gh.encrypted:
@@ -827,6 +1040,12 @@ class HEParty:
             return hist
         pl = gh.paillier
         n = len(gh)
+        if gh.packed:       # one plane
+            longest = int(np.diff(seg_ptr).max()) if n_bins else 0
+            hist = gh._packed_result(pl, pl.reduce_segments(gh.g_enc, seg_ptr, idx),
+                                     packed_bits_after("sum", gh.pt_bits, k=max(1, longest)))
+            hist.bin_encrypted = np.diff(seg_ptr) > 0
+            return hist
         both = np.concatenate([gh.g_enc, gh.h_enc])
         seg2 = np.concatenate([seg_ptr, seg_ptr[1:] + seg_ptr[-1]])
         idx2 = np.concatenate([idx, idx + n])
@@ -852,6 +1071,10 @@ class HEParty:
                 out.h[cut[f]:cut[f + 1]] = np.cumsum(hist.h[cut[f]:cut[f + 1]], dtype=np.float32)
             return out
         pl = hist.paillier
+        if hist.packed:     # one plane
+            widest = int(np.diff(cut).max()) if len(cut) > 1 else 0
+            return hist._packed_result(pl, pl.scan_segments(hist.g_enc, cut),
+                                       packed_bits_after("sum", hist.pt_bits, k=max(1, widest)))
         seg2 = np.concatenate([cut, cut[1:] + n_bins])
         sc = pl.scan_segments(np.concatenate([hist.g_enc, hist.h_enc]), seg2)
         out = GHPairs(np.zeros(n_bins, np.float32), np.zeros(n_bins, np.float32), pl)

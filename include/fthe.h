@@ -443,6 +443,55 @@ int fthe_wire_decode(const uint8_t *in, size_t len, int words, uint32_t *g, uint
 int fthe_encode_fixed_dev(fthe_ctx *ctx, const float *x, size_t count, uint64_t *m);
 int fthe_decode_fixed_dev(fthe_ctx *ctx, const uint64_t *m, size_t count, float *x);
 
+/* ---- packed gradient pairs: one ciphertext per (g, h) (opt-in; not in the reference) ----
+ * GHPair::homo_encrypt (common.h:125-133) spends two ciphertexts on two 64-bit codes.  Here both
+ * codes of a pair share one plaintext ("GH packing"), which halves the ciphertexts of the encrypt,
+ * of the histogram / sibling / prefix loops, of the decrypt, and the wire bytes.  With
+ * code(x) = (int64)((double)x * 1e6), S = FTHE_GH_FIELD_BITS and W = FTHE_GH_PACKED_BITS:
+ *     M = code(g) + code(h) * 2^S  (an integer, possibly negative),   m = M mod 2^W   (six words).
+ * Decode of a plaintext T (any sum or difference of such m, reduced mod n): T mod 2^W; the g
+ * field is the signed low S bits g_s; the h field is ((T - g_s) >> S) mod 2^S; each field's low 64
+ * bits are the code the two-ciphertext flow decrypts, so the decoded floats are bit-identical to it
+ * (the g field holds the true sum of the codes while |sum| < 2^(S-1): any 2^32 addends).
+ * Add, k-way / segmented products, scan, histogram (planes = 1; an Enc(0) is a packed zero) and the
+ * wire codecs work on packed ciphertexts as they are.  Subtraction needs fthe_sub_bits with
+ * bits = W (fthe_sub's exponent 2^64 - 1 leaves m_b 2^64 inside the h field).
+ * Plaintext growth, the one new limit: bits(a + b) <= max(bits a, bits b) + 1 and
+ * bits(a - b) <= max(bits a, bits b + W) + 1; a result decrypts correctly only while its plaintext
+ * is below n (below p for short_pt).  FedTree's flows keep the right-hand side of a subtraction
+ * shallow (father - computed: ~385 bits; sum - last prefix: ~580 bits): within Paillier-2048 in both
+ * decrypt forms and Paillier-1024 in the full form, not within a 512-bit n.
+ * fthe_pack_gh_dev / fthe_unpack_gh_dev   the codec on device arrays: m is count x 6 words; unpack
+ *                      reads the low six words of rows stride_words (>= 6) apart; outputs nullable.
+ * fthe_encrypt_gh_packed   pack, then the encrypt of general plaintexts: r, r_words, rng_seed,
+ *                      index0 and flags exactly as fthe_encrypt_u64_at.  Keys of fewer than six
+ *                      words: FTHE_ERR_ARG.  c: count * 2*n_words words.
+ * fthe_decrypt_gh_packed   decrypt and decode, chunk by chunk (no count x n_words plaintext array);
+ *                      short_pt != 0: fthe_decrypt_short semantics.  Outputs nullable, count each. */
+#define FTHE_GH_FIELD_BITS   96
+#define FTHE_GH_PACKED_BITS  192
+#define FTHE_GH_PACKED_WORDS 6
+int fthe_pack_gh_dev(fthe_ctx *ctx, const float *g, const float *h, size_t count, uint32_t *m);
+int fthe_unpack_gh_dev(fthe_ctx *ctx, const uint32_t *m, int stride_words, size_t count,
+                       float *g, float *h, int64_t *g_code, int64_t *h_code);
+int fthe_encrypt_gh_packed_dev(fthe_key *key, fthe_ctx *ctx, const float *g, const float *h, size_t count,
+                               const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
+                               uint32_t *c, int flags);
+int fthe_encrypt_gh_packed(fthe_key *key, fthe_ctx *ctx, const float *g, const float *h, size_t count,
+                           const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
+                           uint32_t *c, int flags);
+int fthe_decrypt_gh_packed_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *c, size_t count,
+                               float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt);
+int fthe_decrypt_gh_packed(fthe_key *key, fthe_ctx *ctx, const uint32_t *c, size_t count,
+                           float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt);
+/* out[i] = a[i] * b[i]^(2^bits - 1) mod n^2: a - b on plaintexts that live mod 2^bits
+ * (m_b (2^bits - 1) = -m_b mod 2^bits), 8 <= bits <= 32 * n_words, else FTHE_ERR_ARG.  The program
+ * of fthe_sub with an all-ones chain of that length; bits = 64 gives fthe_sub's rows.  Alias-safe. */
+int fthe_sub_bits_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
+                      int bits, uint32_t *out);
+int fthe_sub_bits(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
+                  int bits, uint32_t *out);
+
 /* ---- test hook: the randomness of the direct-y CRT encrypt ----------------
  * A key holder's fthe_encrypt_u64[_dev] with r == NULL draws, per ciphertext,
  * y_p uniform in [1, p) and y_q uniform in [1, q) and computes
