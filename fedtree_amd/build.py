@@ -39,19 +39,24 @@ def build_kernels():
     # A/B generator switches (FTHE_GEN_*: tools/build_m37_ab.sh, the FTHE_GEN_NADIC_AB library A/Bs; some give
     # wrong results by design, e.g. FTHE_GEN_NADIC_AB=noest) reach only a library built elsewhere
     # (FTHE_BUILD_OUT), never the in-tree libfthe.so.  Removed before the generators are imported: some read
-    # their switches at import time.  gen_padic_mfma takes its switches as an argument: read below, after the scrub.
+    # their switches at import time.  gen_padic_mfma, gen_addb and gen_nadicb take theirs as arguments: read below,
+    # after the scrub.
     if OUT == DEFAULT_OUT:
         for k in sorted(k for k in os.environ if k.startswith("FTHE_GEN_")):
             os.environ.pop(k)
             sys.stderr.write(f"build.py: ignoring {k} (A/B generator switch) for the in-tree library\n")
     m37_ab = os.environ.get("FTHE_GEN_M37_AB", "")
+    addb_dbg = os.environ.get("FTHE_GEN_ADDB_DBG", "")
+    nadicb_dbg = os.environ.get("FTHE_GEN_NADICB_DBG", "")
     import gen_montprog  # noqa: E402
     import gen_padic  # noqa: E402
     import gen_nadic  # noqa: E402
     import gen_padic_mfma  # noqa: E402
     import gen_addb  # noqa: E402
     import gen_nadicb  # noqa: E402
-    for lay_name, new_lay in (("addb_layout.h", gen_addb.layout_header()), ("nadicb_layout.h", gen_nadicb.layout_header())):
+    nadicb_waves = int(os.environ.get("FTHE_GEN_NADICB_WAVES", gen_nadicb.WAVES))     # timing builds only
+    for lay_name, new_lay in (("addb_layout.h", gen_addb.layout_header()),
+                              ("nadicb_layout.h", gen_nadicb.layout_header(nadicb_waves))):
         lay = os.path.join(GEN, lay_name)
         if not os.path.exists(lay) or open(lay).read() != new_lay:
             with open(lay, "w") as f:
@@ -77,9 +82,10 @@ def build_kernels():
     kernels.append((2176, "fthe_nadic_m76", "nadic_m76",
                     lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_m76", mont=True)))
     # its matrix-core Barrett form (products on the VALU, both Barrett reductions by n on i8 MFMA): 2276
-    kernels.append((2276, "fthe_nadic_b76", "nadic_b76", lambda: gen_nadicb.gen_nadicb("fthe_nadic_b76")))
+    kernels.append((2276, "fthe_nadic_b76", "nadic_b76",
+                    lambda: gen_nadicb.gen_nadicb("fthe_nadic_b76", nadicb_waves, nadicb_dbg)))
     # the P-2048 ciphertext add with a matrix-core Barrett reduction (not an op-program kernel): blob 3152
-    kernels.append((3152, "fthe_addb_q152", "addb_q152", lambda: gen_addb.gen_addb("fthe_addb_q152")))
+    kernels.append((3152, "fthe_addb_q152", "addb_q152", lambda: gen_addb.gen_addb("fthe_addb_q152", addb_dbg)))
     for S, name, stem, make in kernels:
         asm = os.path.join(GEN, f"{stem}.s")
         src = make()
@@ -115,8 +121,8 @@ def build_kernels():
 def build_lib():
     srcs = [os.path.join(CSRC, "fthe.hip"), os.path.join(CSRC, "fthe_glue.hip"), os.path.join(CSRC, "fthe_hist.hip"),
             os.path.join(CSRC, "fthe_dec.hip"), os.path.join(CSRC, "fthe_wire.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("bn_host.hpp", "fthe_glue.h", "padic_tiles.hpp", "addb_image.hpp",
-                                                    "nadicb_image.hpp")] + \
+    deps = srcs + [os.path.join(CSRC, f) for f in ("bn_host.hpp", "fthe_glue.h", "padic_tiles.hpp", "barrett_image.hpp",
+                                                    "addb_image.hpp", "nadicb_image.hpp")] + \
         [os.path.join(GEN, "montprog_blobs.h"), os.path.join(GEN, "addb_layout.h"), os.path.join(GEN, "nadicb_layout.h"),
          os.path.join(HERE, "..", "include", "fthe.h")]
     cmd = ["/opt/rocm/bin/hipcc", f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17",

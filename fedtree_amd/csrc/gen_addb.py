@@ -44,6 +44,9 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from barrett_mfma import LANE_MASK, active, copy_slot, pair, quad4  # noqa: E402,F401
+import barrett_mfma as bm  # noqa: E402
+from gen_montprog import _descriptor  # noqa: E402
 
 # ---- layout constants shared with the host image builder (fthe.hip addb_image) and tools/addb_model.py ----
 S, Q, B = 152, 38, 27
@@ -80,9 +83,7 @@ NQ1, NQ3 = 129, 129                          # q1, q3 dwords (rows >= N: q3 < 2^
 MU_SHIFT = 4072 + 4128                       # mu = floor(2^(A + C) / N)
 S1_BASE = 512                                # product-1 output byte columns from 512
 BIAS_COL, BIAS_DIGIT = 515, -2               # -2^4121 in product 1's corrections
-M_A = (0, 1, 2, 3, 12, 13, 14, 15)           # rows whose copies sit in slots 0..7 (ds_read_b128 lane groups)
-M_B = (4, 5, 6, 7, 8, 9, 10, 11)             # slots 8..15
-assert IMG_BYTES % 16 == 0 and WAVE_AREA % 16 == 0 and LDS_BYTES <= 160 * 1024
+assert A1_OFF == 0 and IMG_BYTES % 16 == 0 and WAVE_AREA % 16 == 0 and LDS_BYTES <= 160 * 1024
 assert WAVE_AREA >= max(S * RB, 16 * QROW, 16 * GROW) and QROW % 16 == 0 and (QROW // 4) % 32 == 4
 
 
@@ -96,16 +97,6 @@ def layout_header():
     lines = ["// generated by fedtree_amd/build.py from gen_addb.py -- layout of fthe_addb_q152", "#pragma once"]
     lines += [f"constexpr int {k} = {v};" for k, v in vals.items()]
     return "\n".join(lines) + "\n"
-
-
-def copy_slot(m):
-    return M_A.index(m) if m in M_A else 8 + M_B.index(m)
-
-
-def band(nd, s0, k0):
-    """the A tile of output bytes [s0, s0+16) x input bytes [k0, k0+64) has a nonzero digit c[s - k]"""
-    lo, hi = s0 - k0 - 63, s0 + 15 - k0
-    return not (hi < 0 or lo >= nd)
 
 
 # ---- the matrix-core product z = x y (section 2M, "mfz"; tools/addb_mfz_model.py is its bit-exact model) ------
@@ -145,17 +136,33 @@ assert MZ_RY >= 515 and (MZ_RY - MZ_DELTA) % 16 == 0 and (MZ_RY - 127) % 16 == 0
 assert all(x % 16 == 0 for x in (MZ_YS, MZ_GS, MZ_ZS, MZ_WS)) and MZ_YS + MZ_YAREA <= 2048
 
 ND1, ND2 = 515, 513                          # balanced digits of mu and N
-ACT1 = [[kb for kb in range(KB1) if band(ND1, 512 + 16 * t, 64 * kb)] for t in range(TILES1)]
-ACT2 = [[kb for kb in range(KB2) if band(ND2, 16 * t, 64 * kb)] for t in range(TILES2)]
+ACT1 = active(ND1, S1_BASE, TILES1, KB1)
+ACT2 = active(ND2, 0, TILES2, KB2)
 CHUNKS = [list(range(0, 8)), list(range(8, 16)), list(range(16, 24)), list(range(24, 33))]
 
 
-def gen_addb(name: str) -> str:
-    # timing-only knock-outs (wrong results; a library built elsewhere, tools/addb_lib_ab.sh): noprod (no product
-    # MADs), nomfma (no MFMAs), nonorm (no group normalisation), nobarrett (no q1/q3 staging, products, folds),
-    # nocanon (no conditional subtractions); stamp: per-phase s_memtime cycle sums per wave, written after the
-    # launch's output rows (tools/addb_stamps.py; the stamps' lgkmcnt(0) drains cost some overlap)
-    DBG = set(os.environ.get("FTHE_GEN_ADDB_DBG", "").split(","))
+# switches (fedtree_amd/build.py passes FTHE_GEN_ADDB_DBG on, to a library built elsewhere only: tools/addb_lib_ab.sh).
+# Timing-only knock-outs (wrong results): noprod (no product MADs), nomfma (no MFMAs), nonorm (no group
+# normalisation), nobarrett (no q1/q3 staging, products, folds), nocanon (no conditional subtractions), ldsfree
+# (staging at conflict-free addresses), mznorm / mzmfma (mfz's normalisation / MFMAs).  stamp: per-phase s_memtime
+# cycle sums per wave, written after the launch's output rows (tools/addb_stamps.py; the stamps' lgkmcnt(0) drains
+# cost some overlap).  Correct schedules: nokara, nocnd, mfz (below); slowall: every lane through the
+# normalisation's slow path (the emulator's test build).
+SWITCHES = ("noprod", "nomfma", "nonorm", "nobarrett", "nocanon", "ldsfree", "stamp", "slowall", "nocnd", "nokara",
+            "mfz", "mznorm", "mzmfma")
+
+
+def parse_dbg(dbg):
+    return bm.parse_switches(dbg, SWITCHES, "addb")
+
+
+# kernarg (the docstring): x, y, out, kctx; count, workgroups; the x and y index lists
+KARGS = tuple((8 * i, 8, 'global_buffer') for i in range(4)) + ((32, 4, 'by_value'), (36, 4, 'by_value'),
+                                                                (40, 8, 'global_buffer'), (48, 8, 'global_buffer'))
+
+
+def gen_addb(name: str, dbg="") -> str:
+    DBG = parse_dbg(dbg)
     # the product z = x y as one level of Karatsuba (three 76 x 76-limb products, section 2K below) instead of
     # 152 x 152 operand scanning; "nokara" keeps the latter (a correct schedule, for the A/B)
     KARA = "nokara" not in DBG
@@ -207,12 +214,6 @@ def gen_addb(name: str) -> str:
     def Thi(k):
         return f"v{TB + 2 * (k % NT) + 1}"
 
-    def pair(n):
-        return f"v[{n}:{n + 1}]"
-
-    def quad4(n):
-        return f"v[{n}:{n + 3}]"
-
     tmp = pair(V_TMP)
     # ---- SGPRs ---------------------------------------------------------------------------------------
     # s[0:1] kernarg, s2 wg id, s[4:5] x rows, s[6:7] y rows, s[8:9] out rows, s[10:11] kctx, s12 count,
@@ -220,7 +221,6 @@ def gen_addb(name: str) -> str:
     # lane masks: s[20:21] quad lane 3, s[22:23] lane 0, s[24:25] lane 1, s[26:27] lane 2,
     # s[28:29] live lanes, s30 = 256, s31 = 65536, s32 = 2^24, s33 = 0x80808080, s[34:35] x index list,
     # s[36:37] y index list (0: direct rows), s[38:39] carry scratch of the gathered addresses
-    LANE_MASK = {3: "s[20:21]", 0: "s[22:23]", 1: "s[24:25]", 2: "s[26:27]"}
     LIVE = "s[28:29]"
     NSGPR = 68 if "stamp" in DBG else 50 if MFZ else 42   # s[40:41]: the product steps' carry-out sink; MFZ: s42..s48
 
@@ -238,36 +238,11 @@ def gen_addb(name: str) -> str:
     e('  s_load_dword s12, s[0:1], 0x20')
     e('  s_load_dwordx2 s[34:35], s[0:1], 0x28')
     e('  s_load_dwordx2 s[36:37], s[0:1], 0x30')
-    for j, pat in ((3, 0x88888888), (0, 0x11111111), (1, 0x22222222), (2, 0x44444444)):
-        lo, hi = LANE_MASK[j][2:-1].split(':')
-        e(f'  s_mov_b32 s{lo}, {hex(pat)}')
-        e(f'  s_mov_b32 s{hi}, {hex(pat)}')
-    e('  s_movk_i32 s30, 0x100')
-    e('  s_mov_b32 s31, 0x10000')
-    e('  s_mov_b32 s32, 0x1000000')
-    e('  s_mov_b32 s33, 0x80808080')
+    bm.lane_masks(e)
+    bm.fold_consts(e)
     e('  s_waitcnt lgkmcnt(0)')
-    # ---- constant image -> LDS: every thread copies 16 B per pass (768 threads x 16 B = 12,288 B) --------
-    e(f'  v_lshlrev_b32_e32 v{V_ROW}, 4, v{V_TID}')
-    passes = (IMG_BYTES + 64 * WAVES * 16 - 1) // (64 * WAVES * 16)
-    for p in range(passes):
-        off = p * 64 * WAVES * 16
-        part = off + 64 * WAVES * 16 > IMG_BYTES
-        if part:
-            e(f'  v_cmp_gt_u32_e32 vcc, {hex(IMG_BYTES - off)}, v{V_ROW}')
-            e('  s_and_saveexec_b64 s[16:17], vcc')
-        e(f'  v_add_u32_e32 v{V_LDSI}, {hex(off)}, v{V_ROW}')
-        e(f'  global_load_dwordx4 v[8:11], v{V_LDSI}, s[10:11]')
-        e('  s_waitcnt vmcnt(0)')
-        e(f'  ds_write_b128 v{V_LDSI}, v[8:11]')
-        if part:
-            e('  s_mov_b64 exec, s[16:17]')
-    e(f'  v_cmp_eq_u32_e32 vcc, 0, v{V_TID}')                           # thread 0: batch counter = 0
-    e('  s_and_saveexec_b64 s[16:17], vcc')
-    e(f'  v_mov_b32_e32 v{V_TMP}, {hex(LDS_CNT)}')
-    e(f'  v_mov_b32_e32 v{V_TMP + 1}, 0')
-    e(f'  ds_write_b32 v{V_TMP}, v{V_TMP + 1}')
-    e('  s_mov_b64 exec, s[16:17]')
+    # ---- constant image -> LDS (768 threads x 16 B = 12,288 B per pass), batch counter = 0 --------------------
+    bm.image_to_lds(e, IMG_BYTES, WAVES, LDS_CNT, 's[10:11]', 's[16:17]', V_TID, V_ROW, V_LDSI, XB, V_TMP)
     e('  s_waitcnt lgkmcnt(0)')
     e('  s_barrier')
     # ---- the wave's batches of 16 ciphertexts: the k-th batch the workgroup hands out is wg + k * nwg
@@ -290,19 +265,7 @@ def gen_addb(name: str) -> str:
     e(f'  v_and_b32_e32 v{V_TMP + 1}, 15, v{V_TMP}')                   # m (= B column v)
     e(f'  v_lshrrev_b32_e32 v{V_SH}, 4, v{V_TMP}')                     # h
     e(f'  v_lshlrev_b32_e32 v{V_SH}, 4, v{V_SH}')                      # 16 h
-    # copy slot of row m: M_A -> 0..7, M_B -> 8..15: slot = m < 4 ? m : m < 12 ? m + 4 : m - 8
-    e(f'  v_add_u32_e32 v{V_A1}, 4, v{V_TMP + 1}')
-    e(f'  v_subrev_u32_e32 v{V_A2}, 8, v{V_TMP + 1}')
-    e(f'  v_cmp_gt_u32_e32 vcc, 12, v{V_TMP + 1}')
-    e(f'  v_cndmask_b32_e32 v{V_A1}, v{V_A2}, v{V_A1}, vcc')
-    e(f'  v_cmp_gt_u32_e32 vcc, 4, v{V_TMP + 1}')
-    e(f'  v_cndmask_b32_e32 v{V_A1}, v{V_A1}, v{V_TMP + 1}, vcc')         # slot
-    e(f'  v_mul_u32_u24_e32 v{V_A1}, {COPY}, v{V_A1}')
-    e(f'  v_add_u32_e32 v{V_A1}, v{V_A1}, v{V_SH}')                    # slot*COPY + 16 h
-    e(f'  v_add_u32_e32 v{V_A2}, {A2_OFF}, v{V_A1}')
-    if A1_OFF:
-        e(f'  v_add_u32_e32 v{V_A1}, {A1_OFF}, v{V_A1}')
-    e(f'  v_add_u32_e32 v{V_C}, {CORR1_OFF}, v{V_SH}')                 # corrections: + 64 t (+ CORR2-CORR1)
+    bm.copy_addrs(e, V_TMP + 1, V_SH, V_A1, V_A2, V_C, COPY, A2_OFF, CORR1_OFF)
     e(f'  v_mul_u32_u24_e32 v{V_B}, {QROW}, v{V_TMP + 1}')
     e(f'  v_add3_u32 v{V_B}, v{V_B}, v{V_SH}, s15')                    # staging row m + 16 h
     e(f'  v_mul_u32_u24_e32 v{V_G}, {GROW}, v{V_TMP + 1}')
@@ -345,10 +308,6 @@ def gen_addb(name: str) -> str:
     e('  s_mul_i32 s13, s13, s19')
     e('  s_add_u32 s13, s13, s2')
     e('  s_lshl_b32 s13, s13, 4')                                       # first ciphertext of the batch
-    if "prio" in DBG:
-        e('  s_setprio 3')
-    if "prioinv" in DBG:
-        e('  s_setprio 0')
     e('  s_cmp_ge_u32 s13, s12')
     e('  s_cbranch_scc1 .Lend')
     # ROW = g*512 + j*128 = first*512 + lane*128; live lanes: g < count
@@ -502,10 +461,6 @@ def gen_addb(name: str) -> str:
         e(f'  v_mov_b64_e32 {pair(HO)}, 0')
         e(f'  v_mov_b32_e32 v{VMASK}, {hex(MASK)}')
         e(f'  v_cndmask_b32_e64 v{VMASK}, v{VMASK}, 0, s[20:21]')
-        if "prio" in DBG:
-            e('  s_setprio 0')
-        if "prioinv" in DBG:
-            e('  s_setprio 3')
         # ---- 2. z = x y: 152 steps; step i reads a_i (prefetched), adds a_i X into the window, retires the
         #         lowest column: its carry stays in the lane's next column, its low 27 bits go one lane down (the
         #         top column of lane j-1: one v_and_b32 with DPP into the hand-off pair, lane 3 receiving 0, that
@@ -552,10 +507,6 @@ def gen_addb(name: str) -> str:
         e(f'  v_subrev_u32_e32 v{V_LDSI}, {hex(NTRIP * NT * RB)}, v{V_LDSI}')
 
         e('// @phase window')
-        if "prio" in DBG:
-            e('  s_setprio 3')
-        if "prioinv" in DBG:
-            e('  s_setprio 0')
         # ---- 3. window -> W limbs (X), W -> dwords WD; z mod 2^4104 limbs (LDS) -> dwords ZL ---------------
         e(f'  v_mov_b64_e32 {tmp}, 0')
         for k in range(Q):                            # columns 152 + k: T(k), the top one in the hand-off pair
@@ -573,9 +524,8 @@ def gen_addb(name: str) -> str:
     #          A column ends as (P0 low, P2 low).  The combination is signed limb arithmetic, normalised as one
     #          228-limb number (blocks 1..3 of z; block 0 is P0 low) with carries across lanes and blocks. -----
     Q2 = Q // 2                                   # 19 window limbs per lane
-    # the multiplier prefetch after the step's ninth multiply-add (timing knob pfN: after the first measured no
-    # faster, profiles/r05f_addb_libs_ab.jsonl)
-    KARA_PF = next((int(t[2:]) for t in DBG if t.startswith('pf') and t[2:].isdigit()), 8)
+    KARA_PF = 8                                   # the multiplier prefetch after the step's ninth multiply-add (after
+                                                  # the first: no faster, profiles/r05f_addb_libs_ab.jsonl)
     # P1 retires lane 0's column into its quad lane's register with one v_cndmask_b32 whose src0 is the DPP
     # broadcast of lane 0 (vcc = the lanes that keep theirs: the steps' multiply-adds write their carry-outs,
     # always 0, to s[40:41] instead of vcc); "nocnd" keeps the broadcast + v_cndmask_b32_e64 pair (A/B)
@@ -890,17 +840,14 @@ def gen_addb(name: str) -> str:
         e(f'  ds_write_b32 v{V_YS}, v{TT} offset:{MZ_RY - 515 - (MZ_RY - 127 - 16 - 384)}')
         e('  s_mov_b64 exec, -1')
         # ---- A fragments: three reads per tile, then the funnel shift ----
-        q = []
+        issue, wait_for = bm.lds_queue(e)
 
-        def issue(tag, ins):
-            e(ins)
-            q.append(tag)
-
-        def wait_for(tag):
-            if tag in q:
-                i = len(q) - 1 - q[::-1].index(tag)
-                e(f'  s_waitcnt lgkmcnt({min(len(q) - i - 1, 15)})')
-                del q[:i + 1]
+        def funnel(n):
+            wait_for(('a', MZ_TS[n]))
+            ap, r4 = AT[MZ_TS[n]], R4[n % 3]
+            for k in range(4):
+                hi = f"v{ap + k + 1}" if k < 3 else f"v{r4}"
+                e(f'  v_alignbyte_b32 v{ap + k}, {hi}, v{ap + k}, v{V_S}')
         for n, t in enumerate(MZ_TS):
             d = 16 * (t + 1)
             a = AT[t]
@@ -908,19 +855,9 @@ def gen_addb(name: str) -> str:
             issue(('a', t), f'  ds_read2_b32 v[{a + 2}:{a + 3}], v{V_AX} offset0:{d + 2} offset1:{d + 3}')
             issue(('a', t), f'  ds_read_b32 v{R4[n % 3]}, v{V_AX} offset:{4 * (d + 4)}')
             if n >= 2:
-                tp = MZ_TS[n - 2]
-                wait_for(('a', tp))
-                ap, r4 = AT[tp], R4[(n - 2) % 3]
-                for k in range(4):
-                    hi = f"v{ap + k + 1}" if k < 3 else f"v{r4}"
-                    e(f'  v_alignbyte_b32 v{ap + k}, {hi}, v{ap + k}, v{V_S}')
+                funnel(n - 2)
         for n in range(len(MZ_TS) - 2, len(MZ_TS)):
-            tp = MZ_TS[n]
-            wait_for(('a', tp))
-            ap, r4 = AT[tp], R4[n % 3]
-            for k in range(4):
-                hi = f"v{ap + k + 1}" if k < 3 else f"v{r4}"
-                e(f'  v_alignbyte_b32 v{ap + k}, {hi}, v{ap + k}, v{V_S}')
+            funnel(n)
         # ---- B fragments and the MFMAs, by v = 4 u - t ----
         vs = MZ_V
         first = set()
@@ -935,17 +872,8 @@ def gen_addb(name: str) -> str:
         folded = []
 
         def fold(u):
-            since = sum(1 for ln in o[last_mfma[u] + 1:] if ln.startswith('  '))
-            need = 19 - since                                          # XDL -> VALU read (as XDL_WAIT)
-            while need > 0:
-                e(f'  s_nop {min(need, 8) - 1}')
-                need -= 8
-            acc = DA[u]
-            e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc}, 1, 0')
-            e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 1}, s30, {pair(PG)}')
-            e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 2}, s31, {pair(PG)}')
-            e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 3}, s32, {pair(PG)}')
-            issue(('w', u), f'  ds_write_b64 v{V_GW}, {pair(PG)} offset:{512 * u}')
+            bm.settle(e, o, last_mfma[u])                              # XDL -> VALU read
+            bm.fold_tile(issue, e, ('w', u), DA[u], PG, V_GW, 512 * u)
             folded.append(u)
         for n, v in enumerate(vs):
             wait_for(('b', n))
@@ -1064,159 +992,22 @@ def gen_addb(name: str) -> str:
         e(f'  ds_read_b128 {quad4(BQ + 4 * kb)}, v{V_B} offset:{64 * kb}')
     e('  s_waitcnt lgkmcnt(0)')
 
-    # ---- 5/6. the two MFMA products, each folded chunk by chunk into DQ (quad lane j: chunk j) ----------
-    # three accumulator sets (the third in GB, free outside the normalisation): the tiles of a chunk pair as one
-    # stream, tile n - 2 folded right after tile n's first MFMA, so its results have long been written and the
-    # fold waits only for the wait states still missing (as fthe_nadic_b76, gen_nadicb.py); "acc2" keeps two
-    # sets with the fold of tile n - 1 behind fixed s_nop padding (A/B)
-    ACCS = ACC + (GB,) if "acc2" not in DBG else ACC
-    NACC = len(ACCS)
-    XDL_WAIT = 19                                 # wait states after an MFMA before a VALU reads its result
-
-    def mfma_product3(prod):
-        A = V_A1 if prod == 1 else V_A2
-        KO = KO1 if prod == 1 else KO2
-        act = ACT1 if prod == 1 else ACT2
-        corr = 0 if prod == 1 else CORR2_OFF - CORR1_OFF
+    # ---- 5/6. the two MFMA products (barrett_mfma.tile_stream): the tiles of a chunk pair as one stream on three
+    # accumulator sets (the third in GB, free outside the normalisation), folded into the pair's group rows and
+    # normalised into DQ (quad lane j: chunk j)
+    def mfma_product(prod):
+        plan = dict(accs=ACC + (GB,), aop=AOP, bq=BQ, v_c=V_C, pg=PG, v_g=V_G, copy=COPY)
+        plan.update(dict(v_a=V_A1, ko=KO1, corr=0) if prod == 1 else
+                    dict(v_a=V_A2, ko=KO2, corr=CORR2_OFF - CORR1_OFF))
         e(f'  v_mov_b32_e32 v{CR}, 0')
         for jp in range(0, len(CHUNKS), 2):
-            t0 = CHUNKS[jp][0]
-            tiles = tuple(CHUNKS[jp]) + tuple(CHUNKS[jp + 1])
-            ops = [(n, t, kb) for n, t in enumerate(tiles) for kb in act[t]]
-            q = []                                   # outstanding LDS ops, oldest first (tags)
-
-            def issue(tag, ins):
-                e(ins)
-                q.append(tag)
-
-            def wait_for(tag):
-                if tag not in q:
-                    return
-                i = q.index(tag)
-                e(f'  s_waitcnt lgkmcnt({min(len(q) - i - 1, 15)})')
-                del q[:i + 1]
-
-            def read_a(x):
-                n, t, kb = ops[x]
-                off = KO + 16 * (4 * kb - t)
-                assert 0 <= off and off + 48 + 16 <= COPY
-                issue(('a', x), f'  ds_read_b128 {quad4(AOP[x % 4])}, v{A} offset:{off}')
-
-            def read_corr(n, t):
-                issue(('c', n), f'  ds_read_b128 {quad4(ACCS[n % NACC])}, v{V_C} offset:{corr + 64 * t}')
-
-            last_mfma = {}
-
-            def settle(n):
-                """wait states before a VALU read of tile n's accumulators: one per instruction issued since"""
-                since = sum(1 for ln in o[last_mfma[n] + 1:] if ln.startswith('  '))
-                need = XDL_WAIT - since
-                while need > 0:
-                    e(f'  s_nop {min(need, 8) - 1}')
-                    need -= 8
-
-            for n in range(min(NACC, len(tiles))):
-                read_corr(n, tiles[n])
-            for x in range(min(3, len(ops))):
-                read_a(x)
-            for x, (n, t, kb) in enumerate(ops):
-                first = x == 0 or ops[x - 1][0] != n
-                if first:
-                    wait_for(('c', n))
-                wait_for(('a', x))
-                if "nomfma" not in DBG:
-                    e(f'  v_mfma_i32_16x16x64_i8 {quad4(ACCS[n % NACC])}, {quad4(AOP[x % 4])}, {quad4(BQ + 4 * kb)}, '
-                      f'{quad4(ACCS[n % NACC])}')
-                last_mfma[n] = len(o) - 1
-                if x + 3 < len(ops):                 # the buffer MFMA x - 1 read at its issue
-                    read_a(x + 3)
-                if first and n >= NACC - 1:
-                    m = n - (NACC - 1)
-                    settle(m)
-                    fold_tile(ACCS[m % NACC], 4 * (tiles[m] - t0))
-                    q.append(('w', m))
-                    if m + NACC < len(tiles):
-                        read_corr(m + NACC, tiles[m + NACC])
-            for m in range(max(0, len(tiles) - (NACC - 1)), len(tiles)):
-                settle(m)
-                fold_tile(ACCS[m % NACC], 4 * (tiles[m] - t0))
-            e('  s_waitcnt lgkmcnt(0)')
+            def stage(t, t0=CHUNKS[jp][0]):          # group 4 (t - t0) + h of the pair, the second chunk from GCH
+                return 32 * (t - t0) + (GCH - 256 if t - t0 >= 8 else 0)
+            bm.tile_stream(e, o, tuple(CHUNKS[jp]) + tuple(CHUNKS[jp + 1]), ACT1 if prod == 1 else ACT2, stage,
+                           mfma="nomfma" not in DBG, **plan)
             e('// @phase norm')
             if "nonorm" not in DBG:
                 norm_pair(jp, jp + 1)
-            e(f'// @phase prod{prod}')
-
-    def mfma_product(prod):
-        if NACC == 3:
-            mfma_product3(prod)
-            return
-        """The tiles of one product chunk by chunk: every A read is issued two MFMAs ahead into one of four
-        buffers, each tile's corrections (srcC) into its accumulator set right after the fold of the tile
-        that used the set last, and s_waitcnt lgkmcnt(n) waits for exactly the read an MFMA needs (LDS
-        returns in order); tile t-1 is folded after tile t's MFMAs are issued."""
-        A = V_A1 if prod == 1 else V_A2
-        KO = KO1 if prod == 1 else KO2
-        act = ACT1 if prod == 1 else ACT2
-        corr = 0 if prod == 1 else CORR2_OFF - CORR1_OFF
-        e(f'  v_mov_b32_e32 v{CR}, 0')
-        for j, tiles in enumerate(CHUNKS):
-            t0 = CHUNKS[j & ~1][0]                   # groups staged from the pair's first tile
-            ops = [(n, t, kb) for n, t in enumerate(tiles) for kb in act[t]]
-            q = []                                   # outstanding LDS ops, oldest first (tags)
-
-            def issue(tag, ins):
-                e(ins)
-                q.append(tag)
-
-            def wait_for(tag):
-                if tag not in q:                     # completed with a later op already waited for
-                    return
-                i = q.index(tag)
-                left = len(q) - i - 1
-                e(f'  s_waitcnt lgkmcnt({min(left, 15)})')
-                del q[:i + 1]
-
-            def read_a(x):
-                n, t, kb = ops[x]
-                off = KO + 16 * (4 * kb - t)
-                assert 0 <= off and off + 48 + 16 <= COPY
-                issue(('a', x), f'  ds_read_b128 {quad4(AOP[x % 4])}, v{A} offset:{off}')
-
-            def read_corr(n, t):
-                issue(('c', n), f'  ds_read_b128 {quad4(ACC[n % 2])}, v{V_C} offset:{corr + 64 * t}')
-
-            read_corr(0, tiles[0])
-            for x in range(min(2, len(ops))):
-                read_a(x)
-            for x, (n, t, kb) in enumerate(ops):
-                first = x == 0 or ops[x - 1][0] != n
-                if first:
-                    wait_for(('c', n))
-                wait_for(('a', x))
-                if "nomfma" not in DBG:
-                    e(f'  v_mfma_i32_16x16x64_i8 {quad4(ACC[n % 2])}, {quad4(AOP[x % 4])}, {quad4(BQ + 4 * kb)}, '
-                      f'{quad4(ACC[n % 2])}')
-                if x + 2 < len(ops):
-                    read_a(x + 2)
-                last = x + 1 == len(ops) or ops[x + 1][0] != n
-                if last:
-                    if n >= 1:                       # fold tile n-1 (its set is then free for tile n+1)
-                        e('  s_nop 7')
-                        e('  s_nop 7')
-                        fold_tile(ACC[(n - 1) % 2], 4 * (tiles[n - 1] - t0))
-                        q.append(('w', n - 1))
-                    if n + 1 < len(tiles):
-                        read_corr(n + 1, tiles[n + 1])
-            e('  s_nop 7')
-            e('  s_nop 7')
-            e('  s_nop 7')
-            fold_tile(ACC[(len(tiles) - 1) % 2], 4 * (tiles[-1] - t0))
-            if j % 2 == 0:
-                continue                             # the pair's second chunk first
-            e('  s_waitcnt lgkmcnt(0)')
-            e('// @phase norm')
-            if "nonorm" not in DBG:
-                norm_pair(j - 1, j)
             e(f'// @phase prod{prod}')
 
     def norm_pair(ja, jb):
@@ -1237,39 +1028,11 @@ def gen_addb(name: str) -> str:
         e('  s_mov_b64 exec, s[16:17]')
         cv = f"v{CR2}"
         ng = max(na, nb)
-        if "norm1" not in DBG:
-            cv = norm_two_chains(ja, jb, na, ng, cv)
-        else:
-            cv = norm_one_chain(ja, jb, na, nb, ng, cv)
+        cv = norm_two_chains(ja, jb, na, ng, cv)
         e('  s_mov_b64 exec, s[16:17]')
         e(f'  v_mov_b32_e32 v{CR}, {cv}')
         e('  s_mov_b64 exec, -1')
         lane_delivery(ja, jb, nb)
-
-    def norm_one_chain(ja, jb, na, nb, ng, cv):
-        def rd(g):
-            for hh in (0, 1):                             # groups g, g + 1: two ds_read_b64 (8-byte rows)
-                b = GB + 4 * ((g // 2) % 2) + 2 * hh
-                e(f'  ds_read_b64 v[{b}:{b + 1}], v{V_GR} offset:{8 * (g + hh)}')
-        rd(0)
-        rd(2)
-        for g0 in range(0, ng, 2):
-            if g0 == na and nb > na:                 # lane ja's chunk ends (its carry stays in FV + 1)
-                e(f'  s_mov_b64 exec, {LANE_MASK[jb]}')
-            e(f'  s_waitcnt lgkmcnt({2 if g0 + 2 < ng else 0})')
-            for g in (g0, g0 + 1):
-                src = pair(GB + 4 * ((g0 // 2) % 2) + 2 * (g - g0))
-                if g % 2 == 0:
-                    e(f'  v_mad_i64_i32 {pair(DQ + g)}, vcc, {cv}, 1, {src}')
-                    cv = f"v{DQ + g + 1}"
-                else:
-                    e(f'  v_mad_i64_i32 {pair(FV)}, vcc, {cv}, 1, {src}')
-                    e(f'  v_mov_b32_e32 v{DQ + g}, v{FV}')
-                    cv = f"v{FV + 1}"
-            if g0 + 4 < ng:
-                rd(g0 + 4)
-        assert cv == f"v{FV + 1}"
-        return cv
 
     def norm_two_chains(ja, jb, na, ng, cv):
         """each lane's chain split in two interleaved halves (half the dependent v_mad_i64_i32 latency, as
@@ -1277,19 +1040,12 @@ def gen_addb(name: str) -> str:
         A's carry-out is added to B's lowest dword, the rare signed overflow rippling through B's dwords on a slow
         path into B's carry-out, which is returned (the lane's final carry)"""
         H = 16
-        q = []
+        issue, wait_for = bm.lds_queue(e)
 
-        def rd(g, tag):
+        def rd(g):
             b = GB + (8 if g >= H else 0) + 4 * ((g // 2) % 2)
             for hh in (0, 1):                             # groups g, g + 1: two ds_read_b64 (8-byte rows)
-                e(f'  ds_read_b64 v[{b + 2 * hh}:{b + 2 * hh + 1}], v{V_GR} offset:{8 * (g + hh)}')
-                q.append(tag)
-
-        def wait_for(tag):
-            if tag in q:
-                i = len(q) - 1 - q[::-1].index(tag)       # the tag's last read
-                e(f'  s_waitcnt lgkmcnt({min(len(q) - i - 1, 15)})')
-                del q[:i + 1]
+                issue(g, f'  ds_read_b64 v[{b + 2 * hh}:{b + 2 * hh + 1}], v{V_GR} offset:{8 * (g + hh)}')
 
         def link(g, cvx, tmp):
             """group g into dword g: even g -> the pair (DQ g, DQ g+1), odd g through tmp; the next carry"""
@@ -1301,7 +1057,7 @@ def gen_addb(name: str) -> str:
             e(f'  v_mov_b32_e32 v{DQ + g}, v{tmp}')
             return f"v{tmp + 1}"
         for g in (0, 2, H, H + 2):
-            rd(g, g)
+            rd(g)
         ca, cb = cv, "0"
         for i in range(0, max(H, ng - H), 2):
             if H + i == na and ng > na:               # only lane jb's chunk has groups here (A is done)
@@ -1311,13 +1067,13 @@ def gen_addb(name: str) -> str:
                 ca = link(i, ca, FV)
                 ca = link(i + 1, ca, FV)
                 if i + 4 < H:
-                    rd(i + 4, i + 4)
+                    rd(i + 4)
             if H + i < ng:
                 wait_for(H + i)
                 cb = link(H + i, cb, PG)
                 cb = link(H + i + 1, cb, PG)
                 if H + i + 4 < ng:
-                    rd(H + i + 4, H + i + 4)
+                    rd(H + i + 4)
         assert ca == f"v{FV + 1}" and cb == f"v{PG + 1}"
         e('  s_mov_b64 exec, s[16:17]')
         # A's carry into B's lowest dword (both lanes), the overflow rippling on a slow path
@@ -1379,15 +1135,6 @@ def gen_addb(name: str) -> str:
         e(f'  v_add_u32_e32 v{CR}, v{X}, v{CR}')
         e('  s_mov_b64 exec, s[16:17]')
         e(f'{lab}_done:')
-
-    def fold_tile(acc, gl):
-        """acc's 4 int32 rows (output bytes 4h..4h+3 of the tile) -> int64 group -> LDS (group 4 (t - t0) + h, t0
-        the first tile of the chunk pair)"""
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc}, 1, 0')                # sign-extended row 0
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 1}, s30, {pair(PG)}')
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 2}, s31, {pair(PG)}')
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 3}, s32, {pair(PG)}')
-        e(f'  ds_write_b64 v{V_G}, {pair(PG)} offset:{8 * gl + (GCH - 256 if gl >= 32 else 0)}')
 
     e('// @phase prod1')
     mfma_product(1)
@@ -1499,7 +1246,7 @@ def gen_addb(name: str) -> str:
     e('')
     if "stamp" in DBG:
         o = stamp_pass(o)
-    return "\n".join(o) + "\n" + descriptor(name, LDS_BYTES, NVGPR, NSGPR)
+    return "\n".join(o) + "\n" + _descriptor(name, LDS_BYTES, NVGPR, NSGPR, max_wg=64 * WAVES, kargs=KARGS)
 
 
 STAMP_PHASES = ['entry', 'load', 'product', 'window', 'q1stage', 'prod1', 'norm', 'q3stage', 'prod2', 'sub',
@@ -1546,55 +1293,3 @@ def stamp_pass(o):
         else:
             out.append(line)
     return out
-
-
-def descriptor(name, lds_bytes, nvgpr, nsgpr):
-    o = []
-    e = o.append
-    e('.rodata')
-    e('.p2align 6')
-    e(f'.amdhsa_kernel {name}')
-    e(f'  .amdhsa_group_segment_fixed_size {lds_bytes}')
-    e('  .amdhsa_private_segment_fixed_size 0')
-    e('  .amdhsa_kernarg_size 56')
-    e('  .amdhsa_user_sgpr_count 2')
-    e('  .amdhsa_user_sgpr_kernarg_segment_ptr 1')
-    e('  .amdhsa_system_sgpr_workgroup_id_x 1')
-    e('  .amdhsa_system_vgpr_workitem_id 0')
-    e(f'  .amdhsa_next_free_vgpr {nvgpr}')
-    e(f'  .amdhsa_next_free_sgpr {nsgpr}')
-    e(f'  .amdhsa_accum_offset {((nvgpr + 3) // 4) * 4}')
-    e('  .amdhsa_reserve_vcc 1')
-    e('  .amdhsa_ieee_mode 0')
-    e('  .amdhsa_dx10_clamp 0')
-    e('.end_amdhsa_kernel')
-    e('')
-    e('.amdgpu_metadata')
-    e('---')
-    e('amdhsa.kernels:')
-    e('  - .args:')
-    for off_, sz, kind in ((0, 8, 'global_buffer'), (8, 8, 'global_buffer'), (16, 8, 'global_buffer'),
-                           (24, 8, 'global_buffer'), (32, 4, 'by_value'), (36, 4, 'by_value'),
-                           (40, 8, 'global_buffer'), (48, 8, 'global_buffer')):
-        e(f'      - .offset: {off_}')
-        e(f'        .size: {sz}')
-        e(f'        .value_kind: {kind}')
-        if kind == 'global_buffer':
-            e('        .address_space: global')
-    e(f'    .group_segment_fixed_size: {lds_bytes}')
-    e('    .kernarg_segment_align: 8')
-    e('    .kernarg_segment_size: 56')
-    e(f'    .max_flat_workgroup_size: {64 * WAVES}')
-    e(f'    .name: {name}')
-    e('    .private_segment_fixed_size: 0')
-    e(f'    .sgpr_count: {nsgpr + 2}')
-    e(f'    .symbol: {name}.kd')
-    e(f'    .vgpr_count: {nvgpr}')
-    e('    .wavefront_size: 64')
-    e('amdhsa.target: amdgcn-amd-amdhsa--gfx950')
-    e('amdhsa.version:')
-    e('  - 1')
-    e('  - 2')
-    e('...')
-    e('.end_amdgpu_metadata')
-    return "\n".join(o) + "\n"

@@ -463,7 +463,13 @@ def gen(S: int, B: int, U: int, name: str, sqr_unrolled: bool = True) -> str:
 
 
 
-def _descriptor(name, lds_bytes, NVGPR, NSGPR, max_wg=256):
+def _descriptor(name, lds_bytes, NVGPR, NSGPR, max_wg=256, kargs=None):
+    """kargs: the kernarg table (offset, size, value kind), sorted by offset; default: the op-program kernels'"""
+    if kargs is None:
+        kargs = ((0, 8, 'global_buffer'), (8, 8, 'global_buffer'), (16, 8, 'global_buffer'),
+                 (24, 4, 'by_value'), (28, 4, 'by_value'), (32, 4, 'by_value'), (36, 4, 'by_value'))
+        kargs += tuple((40 + 8 * t, 8, 'global_buffer') for t in range(16))
+    kernarg_size = kargs[-1][0] + kargs[-1][1]
     o = []
     e = o.append
     # ---- kernel descriptor ------------------------------------------------
@@ -472,7 +478,7 @@ def _descriptor(name, lds_bytes, NVGPR, NSGPR, max_wg=256):
     e(f'.amdhsa_kernel {name}')
     e(f'  .amdhsa_group_segment_fixed_size {lds_bytes}')
     e('  .amdhsa_private_segment_fixed_size 0')
-    e('  .amdhsa_kernarg_size 168')
+    e(f'  .amdhsa_kernarg_size {kernarg_size}')
     e('  .amdhsa_user_sgpr_count 2')
     e('  .amdhsa_user_sgpr_kernarg_segment_ptr 1')
     e('  .amdhsa_system_sgpr_workgroup_id_x 1')
@@ -490,9 +496,6 @@ def _descriptor(name, lds_bytes, NVGPR, NSGPR, max_wg=256):
     e('---')
     e('amdhsa.kernels:')
     e('  - .args:')
-    kargs = ((0, 8, 'global_buffer'), (8, 8, 'global_buffer'), (16, 8, 'global_buffer'),
-             (24, 4, 'by_value'), (28, 4, 'by_value'), (32, 4, 'by_value'), (36, 4, 'by_value'))
-    kargs += tuple((40 + 8 * t, 8, 'global_buffer') for t in range(16))
     for off_, sz, kind in kargs:
         e(f'      - .offset: {off_}')
         e(f'        .size: {sz}')
@@ -501,7 +504,7 @@ def _descriptor(name, lds_bytes, NVGPR, NSGPR, max_wg=256):
             e('        .address_space: global')
     e(f'    .group_segment_fixed_size: {lds_bytes}')
     e('    .kernarg_segment_align: 8')
-    e('    .kernarg_segment_size: 168')
+    e(f'    .kernarg_segment_size: {kernarg_size}')
     e(f'    .max_flat_workgroup_size: {max_wg}')
     e(f'    .name: {name}')
     e('    .private_segment_fixed_size: 0')

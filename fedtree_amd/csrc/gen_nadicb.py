@@ -33,11 +33,13 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from barrett_mfma import LANE_MASK, active, copy_slot, pair, quad4  # noqa: E402,F401
+import barrett_mfma as bm  # noqa: E402
 from gen_montprog import _descriptor  # noqa: E402
 
 S, Q, B = 76, 19, 27
 MASK = (1 << B) - 1
-WAVES = int(os.environ.get("FTHE_GEN_NADICB_WAVES", "12"))   # timing builds only (FTHE_GEN_*: never in-tree)
+WAVES = 12                       # per workgroup; other counts: the waves argument (timing builds, the emulator)
 CT_PER_WAVE = 16
 RB = 76                          # A-column row: 16 ciphertexts x 4 B + pad; 19 dwords: a quad's four write_rows
                                  # lanes 19 x 19 k = 9 k dwords apart (68 B rows: 3 k, 2- to 3-way conflicts) and
@@ -54,15 +56,8 @@ KB1, KB2 = 5, 5
 BIAS_COL, BIAS_DIGIT = 263, -1
 ND1, ND2 = 262, 257
 CHUNKS = (tuple(range(0, 8)), tuple(range(8, 16)), (16,))
-
-
-def band(nd, s0, k0):
-    lo, hi = s0 - k0 - 63, s0 + 15 - k0
-    return not (hi < 0 or lo >= nd)
-
-
-ACT1 = [[kb for kb in range(KB1) if band(ND1, S1_BASE + 16 * t, 64 * kb)] for t in range(TILES1)]
-ACT2 = [[kb for kb in range(KB2) if band(ND2, 16 * t, 64 * kb)] for t in range(TILES2)]
+ACT1 = active(ND1, S1_BASE, TILES1, KB1)
+ACT2 = active(ND2, 0, TILES2, KB2)
 # copy offsets: the A read of tile t, K-block kb, lane half h is at KO + 16 (4 kb - t) + 16 h of row m's copy
 KO1 = 16 * max(t - 4 * kb for t in range(TILES1) for kb in ACT1[t])
 KO2 = 16 * max(t - 4 * kb for t in range(TILES2) for kb in ACT2[t])
@@ -87,9 +82,7 @@ CSTRIDE = 264                    # chunk k's groups at 264 k: with GROW = 568 th
 QST_OFF = 0                      # staging areas inside the wave area (the A column is dead in the Barretts); the
 GST_OFF = 0                      # groups overlap the q staging, which the B operands have left before the MFMAs
 WAVE_AREA = max(ROWS * RB, QST_OFF + 16 * QROW, GST_OFF + 16 * GROW)
-M_A = (0, 1, 2, 3, 12, 13, 14, 15)
-M_B = (4, 5, 6, 7, 8, 9, 10, 11)
-assert IMG_BYTES % 16 == 0 and WAVE_AREA % 16 == 0 and (QROW // 4) % 32 == 4
+assert A1_OFF == 0 and IMG_BYTES % 16 == 0 and WAVE_AREA % 16 == 0 and (QROW // 4) % 32 == 4
 
 
 def lds_bytes(waves=WAVES):
@@ -100,27 +93,31 @@ def lds_bytes(waves=WAVES):
 assert lds_bytes() <= 160 * 1024
 
 
-def copy_slot(m):
-    return M_A.index(m) if m in M_A else 8 + M_B.index(m)
-
-
-def layout_header():
+def layout_header(waves=WAVES):
     """gen/nadicb_layout.h: the constants of the host image builder (nadicb_image.hpp) and launcher"""
     vals = dict(kNbA=A_BITS, kNbC=C_BITS, kNbNd1=ND1, kNbNd2=ND2, kNbS1Base=S1_BASE, kNbTiles1=TILES1,
                 kNbTiles2=TILES2, kNbNq1=NQ1, kNbNq3=NQ3, kNbBiasCol=BIAS_COL, kNbBiasDigit=BIAS_DIGIT,
                 kNbKO1=KO1, kNbKO2=KO2, kNbCopy=COPY, kNbA1Off=A1_OFF, kNbA2Off=A2_OFF, kNbCorr1Off=CORR1_OFF,
                 kNbCorr2Off=CORR2_OFF, kNbImgBytes=IMG_BYTES, kNbNOff=N_OFF, kNbCtxBytes=CTX_BYTES,
-                kNbWaves=WAVES, kNbPerWg=WAVES * CT_PER_WAVE, kNbLdsBytes=lds_bytes())
+                kNbWaves=waves, kNbPerWg=waves * CT_PER_WAVE, kNbLdsBytes=lds_bytes(waves))
     lines = ["// generated by fedtree_amd/build.py from gen_nadicb.py -- layout of fthe_nadic_b76", "#pragma once"]
     lines += [f"constexpr int {k} = {v};" for k, v in vals.items()]
     return "\n".join(lines) + "\n"
 
 
-def gen_nadicb(name: str, waves: int = WAVES) -> str:
-    # timing-only switches (wrong results; fedtree_amd/build.py never lets FTHE_GEN_* reach the in-tree library):
-    # noprod (no VALU product steps), nobarrett (no reductions), nomfma (no MFMAs), noconv (no z -> dword moves),
-    # nonorm (no group normalisation)
-    DBG = set(os.environ.get("FTHE_GEN_NADICB_DBG", "").split(","))
+# timing-only switches (wrong results; fedtree_amd/build.py passes FTHE_GEN_NADICB_DBG on, to a library built elsewhere
+# only): noprod (no VALU product steps), nobarrett (no reductions), nomfma (no MFMAs), noconv (no z -> dword moves),
+# nonorm (no group normalisation), ldsfree (staging at conflict-free addresses), nopreload (the MFMAs' first operands
+# read after the staging), noq3 (z2 without q3_1); stamp: per-phase s_memtime sums (tools/nadicb_stamps.py)
+SWITCHES = ("noprod", "nobarrett", "nomfma", "noconv", "nonorm", "ldsfree", "nopreload", "noq3", "stamp")
+
+
+def parse_dbg(dbg):
+    return bm.parse_switches(dbg, SWITCHES, "nadicb")
+
+
+def gen_nadicb(name: str, waves: int = WAVES, dbg="") -> str:
+    DBG = parse_dbg(dbg)
     DPP = "row_mask:0xf bank_mask:0xf"
     LDSB = lds_bytes(waves)
     LDS_CNT = LDSB - 16                 # the workgroup's batch counter
@@ -141,9 +138,6 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     DQ = 124                          # chunk dwords v124..v155 (the carry rides in DQ + g + 1 until g + 1 is done)
     GB = 156                          # group read buffers: 2 x (2 int64) = v156..v163, ds_read_b128 each
     PG = FV = 164                     # int64 pair (the fold's group; the normalisation's odd-group sum)
-    ACCS = ACC + (GB,) if "acc2" not in DBG else ACC   # MFMA accumulator sets (GB is free until the norm)
-    NACC = len(ACCS)
-    XDL_WAIT = 19                     # wait states after an MFMA before a VALU reads its result (as before)
     CR = 166                          # chunk carry
     NVGPR = 168
     assert T2B + 2 * NT <= V_AI[0] and V_A2X < NVGPR
@@ -152,12 +146,6 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     # window, dead by then); z2's window (the T2 ring) is read by DPP while z1 converts
     NV, DD = 80, 100                  # CANON: n's quarter (19), difference (19)
     YT = 52                           # MUL: the y digits loaded from the slot (38, ring area)
-
-    def pair(n):
-        return f"v[{n}:{n + 1}]"
-
-    def quad4(n):
-        return f"v[{n}:{n + 3}]"
 
     def X0(k):
         return f"v{X0B + k}"
@@ -172,7 +160,6 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     # lane 3, s[22:23] lane 0, s[24:25] lane 1, s[26:27] lane 2, s[28:29] lanes 0-1, s30 = 256, s31 = 65536,
     # s32 = 2^24, s33 = 0x80808080, s[34:35] saved exec, s36 ctx lo + N_OFF, s[40:41] the program's first op,
     # s42 workgroups launched, s43 batches of 16 ciphertexts, s44 scratch
-    LANE_MASK = {3: "s[20:21]", 0: "s[22:23]", 1: "s[24:25]", 2: "s[26:27]"}
     NSGPR = 72 if "stamp" in DBG else 46
 
     o = []
@@ -188,55 +175,16 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     e('  s_load_dwordx2 s[6:7], s[0:1], 0x8')
     e('  s_load_dwordx2 s[8:9], s[0:1], 0x10')
     e('  s_load_dwordx2 s[10:11], s[0:1], 0x18')
-    for j, pat in ((3, 0x88888888), (0, 0x11111111), (1, 0x22222222), (2, 0x44444444)):
-        lo, hi = LANE_MASK[j][2:-1].split(':')
-        e(f'  s_mov_b32 s{lo}, {hex(pat)}')
-        e(f'  s_mov_b32 s{hi}, {hex(pat)}')
+    bm.lane_masks(e)
     e('  s_mov_b32 s28, 0x33333333')
     e('  s_mov_b32 s29, 0x33333333')
-    e('  s_movk_i32 s30, 0x100')
-    e('  s_mov_b32 s31, 0x10000')
-    e('  s_mov_b32 s32, 0x1000000')
-    e('  s_mov_b32 s33, 0x80808080')
+    bm.fold_consts(e)
     e('  s_waitcnt lgkmcnt(0)')
-    # ---- constant image -> LDS: every thread copies 16 B per pass -----------------------------------------
-    e(f'  v_lshlrev_b32_e32 v{V_ROW}, 4, v{V_LANE}')
-    per = 64 * waves * 16
-    for p in range((IMG_BYTES + per - 1) // per):
-        off = p * per
-        part = off + per > IMG_BYTES
-        if part:
-            e(f'  v_cmp_gt_u32_e32 vcc, {hex(IMG_BYTES - off)}, v{V_ROW}')
-            e('  s_and_saveexec_b64 s[34:35], vcc')
-        e(f'  v_add_u32_e32 v{V_LDSI}, {hex(off)}, v{V_ROW}')
-        e(f'  global_load_dwordx4 v[{X0B}:{X0B + 3}], v{V_LDSI}, s[8:9]')
-        e('  s_waitcnt vmcnt(0)')
-        e(f'  ds_write_b128 v{V_LDSI}, v[{X0B}:{X0B + 3}]')
-        if part:
-            e('  s_mov_b64 exec, s[34:35]')
-    e(f'  v_cmp_eq_u32_e32 vcc, 0, v{V_LANE}')                            # thread 0: batch counter = 0
-    e('  s_and_saveexec_b64 s[34:35], vcc')
-    e(f'  v_mov_b32_e32 v{V_TMP}, {hex(LDS_CNT)}')
-    e(f'  v_mov_b32_e32 v{V_TMP + 1}, 0')
-    e(f'  ds_write_b32 v{V_TMP}, v{V_TMP + 1}')
-    e('  s_mov_b64 exec, s[34:35]')
+    # ---- constant image -> LDS, batch counter = 0 ----------------------------------------------------------
+    bm.image_to_lds(e, IMG_BYTES, waves, LDS_CNT, 's[8:9]', 's[34:35]', V_LANE, V_ROW, V_LDSI, X0B, V_TMP)
     e('  s_load_dwordx2 s[42:43], s[0:1], 0x20')                         # live ciphertexts, workgroups launched
     e('  s_waitcnt lgkmcnt(0)')
     e('  s_barrier')
-    # desyncN (timing knob): the waves w, w + 4, w + 8 of a workgroup share a SIMD; the second and third start
-    # N and 2N s_sleep 127 (~8K cycles each) late, so their matrix phases meet the others' product passes.
-    # Measured neutral to slower (659-661 vs 657.6-658.1 ms per 393,216, profiles/r05t_nadicb_desync_ab.jsonl):
-    # the persistent waves' batch draws already spread their phases, so off
-    DSN = next((int(t[6:]) for t in DBG if t.startswith('desync') and t[6:].isdigit()), 0)
-    if DSN:
-        e(f'  v_readfirstlane_b32 s44, v{V_LANE}')
-        e('  s_lshr_b32 s44, s44, 8')                                         # wave / 4 = slot on its SIMD
-        for k in (1, 2):
-            e(f'  s_cmp_lt_u32 s44, {k}')
-            e(f'  s_cbranch_scc1 .Ldesync_{k}')
-            for _ in range(DSN):
-                e('  s_sleep 127')
-            e(f'.Ldesync_{k}:')
     e('// @stampinit')
     e('  s_add_u32 s44, s42, 15')
     e('  s_lshr_b32 s44, s44, 4')                                         # batches of 16 ciphertexts
@@ -266,16 +214,7 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     e(f'  v_and_b32_e32 v{V_TMP + 1}, 15, v{V_LANE}')                  # m
     e(f'  v_lshrrev_b32_e32 v{V_B}, 4, v{V_LANE}')
     e(f'  v_lshlrev_b32_e32 v{V_B}, 4, v{V_B}')                        # 16 h
-    e(f'  v_add_u32_e32 v{V_A1}, 4, v{V_TMP + 1}')
-    e(f'  v_subrev_u32_e32 v{V_A2}, 8, v{V_TMP + 1}')
-    e(f'  v_cmp_gt_u32_e32 vcc, 12, v{V_TMP + 1}')
-    e(f'  v_cndmask_b32_e32 v{V_A1}, v{V_A2}, v{V_A1}, vcc')
-    e(f'  v_cmp_gt_u32_e32 vcc, 4, v{V_TMP + 1}')
-    e(f'  v_cndmask_b32_e32 v{V_A1}, v{V_A1}, v{V_TMP + 1}, vcc')      # copy slot of row m
-    e(f'  v_mul_u32_u24_e32 v{V_A1}, {COPY}, v{V_A1}')
-    e(f'  v_add_u32_e32 v{V_A1}, v{V_A1}, v{V_B}')                     # slot*COPY + 16 h
-    e(f'  v_add_u32_e32 v{V_A2}, {A2_OFF}, v{V_A1}')
-    e(f'  v_add_u32_e32 v{V_C}, {CORR1_OFF}, v{V_B}')                  # corrections + 16 h
+    bm.copy_addrs(e, V_TMP + 1, V_B, V_A1, V_A2, V_C, COPY, A2_OFF, CORR1_OFF)
     e(f'  v_lshrrev_b32_e32 v{V_G}, 1, v{V_B}')                        # 8 h
     e(f'  v_mul_u32_u24_e32 v{V_TMP}, {GROW}, v{V_TMP + 1}')
     e(f'  v_add_u32_e32 v{V_G}, v{V_G}, v{V_TMP}')
@@ -554,10 +493,6 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
 
         e(f'{lab}:')
         e('// @phase product')
-        if "prio" in DBG:                        # timing knobs: the product pass at low / high priority
-            e('  s_setprio 0')
-        if "prioinv" in DBG:
-            e('  s_setprio 3')
         for k in range(NT):
             e(f'  v_mov_b64_e32 {T(T1B, k)}, 0')
             e(f'  v_mov_b64_e32 {T(T2B, k)}, 0')
@@ -593,10 +528,6 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
             e(f'{lab}_skip:')
         e('  s_waitcnt lgkmcnt(0)')
         e('// @phase window')
-        if "prio" in DBG:
-            e('  s_setprio 3')
-        if "prioinv" in DBG:
-            e('  s_setprio 0')
         # ---- normalise both windows: positions TL .. TL + 18 -> 19 limbs (z limbs 76 + 19 k + j) --------
         for tb, tag in ((T1B, 'n1'), (T2B, 'n2')):
             e(f'  v_mov_b64_e32 {tmp}, 0')
@@ -665,107 +596,27 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
         k = next(i for i, ch in enumerate(CHUNKS) if t in ch)
         return CSTRIDE * k + 32 * (t - CHUNKS[k][0])
 
-    def fold_tile(acc, off):
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc}, 1, 0')
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 1}, s30, {pair(PG)}')
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 2}, s31, {pair(PG)}')
-        e(f'  v_mad_i64_i32 {pair(PG)}, vcc, v{acc + 3}, s32, {pair(PG)}')
-        e(f'  ds_write_b64 v{V_G}, {pair(PG)} offset:{off}')
+    TILES = tuple(t for ch in CHUNKS for t in ch)
 
-    def mfma_consts(prod):
-        """A-copy base register, its K offset, the active K-blocks per tile, the corrections' offset"""
-        return ((V_A1, KO1, ACT1, 0) if prod == 1 else (V_A2, KO2, ACT2, CORR2_OFF - CORR1_OFF))
-
-    def first_reads(prod, issue):
-        """chunk 0's first corrections and A operands: constant image rows, independent of the staging, so the
-        stage issues them ahead of its own writes (preload) and their round trip overlaps the staging's"""
-        A, KO, act, corr = mfma_consts(prod)
-        tiles = CHUNKS[0]
-        ops = [(n, t, kb) for n, t in enumerate(tiles) for kb in act[t]]
-        for n in range(min(NACC, len(tiles))):
-            issue(('c', n), f'  ds_read_b128 {quad4(ACCS[n % NACC])}, v{V_C} offset:{corr + 64 * tiles[n]}')
-        for x in range(min(3, len(ops))):
-            n, t, kb = ops[x]
-            off = KO + 16 * (4 * kb - t)
-            assert 0 <= off and off + 64 <= COPY
-            issue(('a', x), f'  ds_read_b128 {quad4(AOP[x % 4])}, v{A} offset:{off}')
+    def mfma_plan(prod):
+        plan = dict(accs=ACC + (GB,), aop=AOP, bq=BQ, v_c=V_C, pg=PG, v_g=V_G, copy=COPY)    # GB: free until the norm
+        plan.update(dict(v_a=V_A1, ko=KO1, corr=0) if prod == 1 else dict(v_a=V_A2, ko=KO2, corr=CORR2_OFF - CORR1_OFF))
+        return (ACT1 if prod == 1 else ACT2), plan
 
     def preload(prod):
+        """the stream's first corrections and A operands ahead of the stage's own writes (bm.first_reads)"""
         if "nopreload" not in DBG:
-            first_reads(prod, lambda tag, ins: e(ins))
+            act, plan = mfma_plan(prod)
+            bm.first_reads(lambda tag, ins: e(ins), TILES, act, **plan)
 
     def mfma_product(prod):
+        """all 17 tiles as one stream (bm.tile_stream; the folds stage each tile's groups at its chunk's offset): no
+        drain of the MFMA pipeline and no exposed operand round trip at the chunk boundaries; its first reads
+        arrived with the stage (its lgkmcnt(0))"""
         e(f'// @phase mfma{prod}')
-        A, KO, act, corr = mfma_consts(prod)
+        act, plan = mfma_plan(prod)
         e(f'  v_mov_b32_e32 v{CR}, 0')
-        # all 17 tiles as one stream (the folds stage each tile's groups at its chunk's offset): no drain of the
-        # MFMA pipeline and no exposed operand round trip at the chunk boundaries (chunkloop: one loop per chunk)
-        for j, tiles in enumerate(CHUNKS if "chunkloop" in DBG else [tuple(t for ch in CHUNKS for t in ch)]):
-            ops = [(n, t, kb) for n, t in enumerate(tiles) for kb in act[t]]
-            q = []
-
-            def issue(tag, ins):
-                e(ins)
-                q.append(tag)
-
-            def wait_for(tag):
-                if tag not in q:
-                    return
-                i = q.index(tag)
-                e(f'  s_waitcnt lgkmcnt({min(len(q) - i - 1, 15)})')
-                del q[:i + 1]
-
-            def read_a(x):
-                n, t, kb = ops[x]
-                off = KO + 16 * (4 * kb - t)
-                assert 0 <= off and off + 64 <= COPY
-                issue(('a', x), f'  ds_read_b128 {quad4(AOP[x % 4])}, v{A} offset:{off}')
-
-            def read_corr(n, t):
-                issue(('c', n), f'  ds_read_b128 {quad4(ACCS[n % NACC])}, v{V_C} offset:{corr + 64 * t}')
-
-            # A operands are read three MFMAs ahead into four buffers (the buffer re-filled after MFMA x is MFMA
-            # x - 1's, whose operands were read at its issue).  Three accumulator sets: tile n - 2 is folded right after tile n's first MFMA, so its results have
-            # long been written (tile n - 1's MFMAs and reads in between) and the fold needs no s_nop padding
-            # unless the instructions since its last MFMA number under XDL_WAIT; tile n + 1's corrections (srcC,
-            # the set tile n - 2 used) are read right after that fold
-            last_mfma = {}
-
-            def settle(n):
-                """wait states before a VALU read of tile n's accumulators: one per instruction issued since"""
-                since = sum(1 for ln in o[last_mfma[n] + 1:] if ln.startswith('  '))
-                need = XDL_WAIT - since
-                while need > 0:
-                    e(f'  s_nop {min(need, 8) - 1}')
-                    need -= 8
-
-            if j > 0 or "nopreload" in DBG:              # chunk 0's arrived with the stage (its lgkmcnt(0))
-                for n in range(min(NACC, len(tiles))):
-                    read_corr(n, tiles[n])
-                for x in range(min(3, len(ops))):
-                    read_a(x)
-            for x, (n, t, kb) in enumerate(ops):
-                first = x == 0 or ops[x - 1][0] != n
-                if first:
-                    wait_for(('c', n))
-                wait_for(('a', x))
-                if "nomfma" not in DBG:
-                    e(f'  v_mfma_i32_16x16x64_i8 {quad4(ACCS[n % NACC])}, {quad4(AOP[x % 4])}, '
-                      f'{quad4(BQ + 4 * kb)}, {quad4(ACCS[n % NACC])}')
-                last_mfma[n] = len(o) - 1
-                if x + 3 < len(ops):
-                    read_a(x + 3)
-                if first and n >= NACC - 1:
-                    m = n - (NACC - 1)
-                    settle(m)
-                    fold_tile(ACCS[m % NACC], stage_off(tiles[m]))              # every chunk staged
-                    q.append(('w', m))
-                    if m + NACC < len(tiles):
-                        read_corr(m + NACC, tiles[m + NACC])
-            for m in range(max(0, len(tiles) - (NACC - 1)), len(tiles)):
-                settle(m)
-                fold_tile(ACCS[m % NACC], stage_off(tiles[m]))
-        e('  s_waitcnt lgkmcnt(0)')
+        bm.tile_stream(e, o, TILES, act, stage_off, preloaded="nopreload" not in DBG, mfma="nomfma" not in DBG, **plan)
         if "nonorm" not in DBG:
             normalise_chunks()
 
@@ -1085,8 +936,7 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     clamp('.Lnoclamp1')
     e('// @phase q3add')
     # z2 += q3_1: Z2 local i += DQ[i + 1] (i < 31), local 31 += the next lane's DQ[0]
-    _dbg_noq3 = os.environ.get("FTHE_GEN_NADICB_DBG") == "noq3"
-    if _dbg_noq3:
+    if "noq3" in DBG:
         e('  s_branch .Ldbg_skip_q3')
     e('  s_nop 4')                                                      # EXEC written by SALU (clamp) -> DPP
     e(f'  v_mov_b32_dpp v{V_TMP}, v{DQ} quad_perm:[1,2,3,3] {DPP}')
@@ -1097,7 +947,7 @@ def gen_nadicb(name: str, waves: int = WAVES) -> str:
     e(f'  v_addc_co_u32_e32 v{Z2B + 31}, vcc, v{Z2B + 31}, v{V_TMP}, vcc')
     e(f'  v_cndmask_b32_e64 v{V_TMP}, 0, 1, vcc')                       # carry out of local 31
     carry_ripple('.Lzc', Z2B, 32, V_TMP, V_TMP + 1)
-    if _dbg_noq3:
+    if "noq3" in DBG:
         e('.Ldbg_skip_q3:')
     stage_q3()
     mfma_product(2)
@@ -1132,7 +982,7 @@ STAMP_PHASES = ['batch', 'ops', 'product', 'window', 'conv', 'stage', 'mfma1', '
 
 
 def stamp_pass(o, waves):
-    """timing build (FTHE_GEN_NADICB_DBG=stamp, tools/nadicb_stamps.py): at every `// @phase` marker the
+    """timing build (switch stamp, tools/nadicb_stamps.py): at every `// @phase` marker the
     s_memtime ticks since the last one go to the accumulator of the phase that ran (s50, runtime: the op loop
     jumps, so the textual order is not the running order; SGPR-relative s_movrels / s_movreld on M0); after the
     last batch lane 0 writes 16 dwords per wave at kernarg rows[15] + 64 (waves wg + wave): the 11 sums, the
@@ -1177,7 +1027,8 @@ if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument('--waves', type=int, default=WAVES)
+    ap.add_argument('--dbg', default="", help="switches: " + ", ".join(SWITCHES))
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:
-        f.write(gen_nadicb('fthe_nadic_b76', a.waves))
+        f.write(gen_nadicb('fthe_nadic_b76', a.waves, a.dbg))

@@ -132,13 +132,12 @@ def test_matrix_core_product_model():
         assert mm.product(x, y)[0] == x * y
 
 
-def test_matrix_core_product_kernel_on_wave_emulator(monkeypatch):
+def test_matrix_core_product_kernel_on_wave_emulator():
     """the "mfz" build of fthe_addb_q152 (the product on the matrix cores, a measured A/B variant: bit-exact on the
     GPU, slower) on the emulator: 16 adds incl. (N - 1)^2, 0 y, 1 1 and the all-ones rows >= N"""
     import gen_addb as ga
     import wave_emu
-    monkeypatch.setenv("FTHE_GEN_ADDB_DBG", "mfz")
-    asm = ga.gen_addb('fthe_addb_q152')
+    asm = ga.gen_addb('fthe_addb_q152', "mfz")
     assert '.Lmz_ct' in asm
     rng = random.Random(29)
     n = am.rand_n(rng)

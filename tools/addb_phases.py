@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Dynamic instruction counts of fthe_addb_q152 by phase (the generator's `// @phase` markers), from one
-emulated workgroup of tools/wave_emu.py: where a batch of 16 adds spends its wave-instructions."""
+emulated workgroup of tools/wave_emu.py: where a batch of 16 adds spends its wave-instructions.
+    python tools/addb_phases.py [SWITCHES]      (gen_addb's, e.g. nokara)"""
 import collections
 import os
 import sys
@@ -28,8 +29,8 @@ def phase_map(asm):
     return pcs
 
 
-def main():
-    asm = ga.gen_addb('fthe_addb_q152')
+def main(dbg=""):
+    asm = ga.gen_addb('fthe_addb_q152', dbg)
     pm = phase_map(asm)
     cnt = collections.defaultdict(collections.Counter)
     orig = wave_emu.Wave.step
@@ -40,7 +41,7 @@ def main():
         cnt[pm[self.pc - 1]][kind] += 1
         return orig(self, op, a)
     wave_emu.Wave.step = step
-    wave_emu.selftest(ntests=16, count0=16)
+    wave_emu.selftest(ntests=16, count0=16, dbg=dbg)
     tot = collections.Counter()
     for c in cnt.values():
         tot.update(c)
@@ -51,4 +52,4 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    main(*sys.argv[1:2])

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Dynamic instruction counts of fthe_nadic_b76 by phase (the generator's `// @phase` markers), from one emulated
 wave (tools/wave_emu.py nadicb_selftest: LOADX; CANON; 2 SQR; 2 MUL; CANON; STOREX on 16 ciphertexts): where a
-product's wave-instructions go."""
+product's wave-instructions go.
+    python tools/nadicb_phases.py [SWITCHES]      (gen_nadicb's, e.g. nopreload)"""
 import collections
 import os
 import sys
@@ -14,8 +15,8 @@ import wave_emu  # noqa: E402
 from addb_phases import phase_map  # noqa: E402
 
 
-def main():
-    pm = phase_map(gb.gen_nadicb('fthe_nadic_b76', waves=1))
+def main(dbg=""):
+    pm = phase_map(gb.gen_nadicb('fthe_nadic_b76', 1, dbg))
     cnt = collections.defaultdict(collections.Counter)
     orig = wave_emu.Wave.step
 
@@ -25,7 +26,7 @@ def main():
         cnt[pm[self.pc - 1]][kind] += 1
         return orig(self, op, a)
     wave_emu.Wave.step = step
-    wave_emu.nadicb_selftest(seed=3, waves=1, batches=1)
+    wave_emu.nadicb_selftest(seed=3, waves=1, batches=1, dbg=dbg)
     tot = collections.Counter()
     for c in cnt.values():
         tot.update(c)
@@ -36,4 +37,4 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    main(*sys.argv[1:2])

@@ -688,14 +688,15 @@ def addb_run(n, xs, ys, asm=None):
     return [mem.read(OB + 512 * i, 512) for i in range(count)]
 
 
-def selftest(ntests=16, count0=None):
+def selftest(ntests=16, count0=None, dbg=""):
+    """dbg: gen_addb's switches (the correct schedules: nokara, nocnd, mfz, slowall)"""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
     sys.path.insert(0, here)
     import gen_addb as ga
     import addb_model as am
     rng = random.Random(5)
-    asm = ga.gen_addb('fthe_addb_q152')
+    asm = ga.gen_addb('fthe_addb_q152', dbg)
     for trial, n in enumerate((am.rand_n(rng), (1 << 2047) + 1, am.rand_n(rng))):
         gather = trial == 2                           # operand rows through index lists (-1: the integer 1)
         N = n * n
@@ -746,7 +747,7 @@ def selftest(ntests=16, count0=None):
     print("wave_emu selftest OK")
 
 
-def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
+def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1, dbg=""):
     """one wave of fthe_nadic_b76 (a workgroup generated with one wave: 16 ciphertexts): LOADX r; CANON;
     STOREX T; SQR 1; STOREX U (digits up to 3n); SQR 1; MUL U; MUL T; CANON; STOREX OUT -> r^7 mod n^2 as
     canonical digits, against Python integers (r: 0, 1, n - 1, random)"""
@@ -761,7 +762,7 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1):
     S, L, B = 152, 16 * waves * batches, 27       # batches > 1: the waves draw several (the emulator runs the
     #                                              first wave to its end, so wave 0 takes them all)
     count = max(count, L) if waves > 1 or batches > 1 else count
-    asm = gb.gen_nadicb('fthe_nadic_b76', waves=waves)
+    asm = gb.gen_nadicb('fthe_nadic_b76', waves, dbg)
     nv = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', asm).group(1))
     lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
     ctx = bytearray(gb.CTX_BYTES)
@@ -948,6 +949,8 @@ if __name__ == '__main__':
         sys.exit(1 if nadicb_selftest(waves=int(sys.argv[2]) if len(sys.argv) > 2 else 1) else 0)
     if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s', 'm37l'):
         sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None, variant=sys.argv[1]) else 0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'addb':          # addb nokara,slowall: a switch string of gen_addb
+        selftest(dbg=",".join(sys.argv[2:]))
     elif len(sys.argv) > 1:                   # e.g. 211: wave 0 takes a second batch (the grid-stride loop)
         selftest(ntests=int(sys.argv[1]), count0=int(sys.argv[1]))
     else:
