@@ -127,6 +127,15 @@ _PROTOS = {
     "fthe_decrypt_gh_packed": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P, _I]),
     "fthe_sub_bits_dev": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
     "fthe_sub_bits": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
+    "fthe_gh_slots": (_I, [_P, _I, _I]),
+    "fthe_pack_gh_slots_dev": (_I, [_P, _P, _P, _SZ, _I, _I, _P]),
+    "fthe_unpack_gh_slots_dev": (_I, [_P, _P, _I, _SZ, _I, _I, _P, _P, _P, _P]),
+    "fthe_encrypt_gh_slots_dev": (_I, [_P, _P, _P, _P, _SZ, _I, _P, _I, _U64, _P, _I, _I]),
+    "fthe_encrypt_gh_slots": (_I, [_P, _P, _P, _P, _SZ, _I, _P, _I, _U64, _P, _I, _I]),
+    "fthe_decrypt_gh_slots_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _P, _P, _P, _I, _I]),
+    "fthe_decrypt_gh_slots": (_I, [_P, _P, _P, _SZ, _I, _P, _P, _P, _P, _I, _I]),
+    "fthe_compress_gh_slots_dev": (_I, [_P, _P, _P, _SZ, _I, _P, _I]),
+    "fthe_compress_gh_slots": (_I, [_P, _P, _P, _SZ, _I, _P, _I]),
     "fthe_last_kernel_ms": (ctypes.c_double, [_P]),
     "fthe_last_montmuls": (ctypes.c_double, [_P]),
     "fthe_kernel_limbs": (_I, [_I]),

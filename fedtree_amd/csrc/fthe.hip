@@ -288,8 +288,8 @@ struct fthe_ctx {
     DevBuf hb[6];                           // histogram CSR / segmented-product plan (device)
     DevBuf ezm;                             // zero-first folds: Enc(0) rows masked to the populated segments
     DevBuf dec[3];                          // decimal codec: 9-digit chunks, lengths, leading chunk / error flag
-    DevBuf gh[3];                           // packed pairs: plaintext words of an encrypt, one decrypt chunk's
-                                            // plaintext words, the host forms' floats / codes
+    DevBuf gh[3];                           // packed / slot-packed pairs: plaintext words of an encrypt, one decrypt
+                                            // chunk's plaintext words, the host forms' floats / codes
     void *cub_tmp = nullptr; size_t cub_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_mm = 0;
@@ -3147,7 +3147,10 @@ extern "C" int fthe_encrypt_words_dev(fthe_key *k, fthe_ctx *c, const uint32_t *
 // Packed gradient pairs (fthe_decrypt_gh_packed): instead of m_low / m_full rows, each chunk's plaintexts go,
 // cut to their low kGhRowWords words, into a chunk-sized context buffer and are decoded from there
 // (k_unpack_gh) into the caller's device arrays (nullable) -- no count x n_words plaintext array.
-struct GhOut { float *g, *h; int64_t *g_code, *h_code; };
+// Slot-packed pairs (fthe_decrypt_gh_slots; slots > 0): the rows kept are slots * slot_words words wide and
+// hold `bins` pairs in plane order over the whole call's `count` rows, so a chunk is decoded with its row
+// offset (k_unpack_gh_slots), each bin into its own element of the whole call's outputs.
+struct GhOut { float *g, *h; int64_t *g_code, *h_code; int slots = 0, slot_words = 0; size_t bins = 0; };
 constexpr int kGhRowWords = 8;          // the six packed words, rounded up to the 16-byte stores of mul_add_out
 
 static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, uint64_t *m_low,
@@ -3155,6 +3158,7 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
     if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
     if (!k->priv) return FTHE_ERR_NOPRIV;
     if (gh && (m_low || m_full || k->n_words < FTHE_GH_PACKED_WORDS)) return FTHE_ERR_ARG;
+    if (gh && gh->slots && (size_t)gh->slots * gh->slot_words > (size_t)k->n_words) return FTHE_ERR_ARG;
     // Batches that leave most of the chip idle (a GHPair from decrypt_gh, one tree node's sums) run the
     // c^(q-1) mod q^2 exponentiation beside c^(p-1) mod p^2, or both on the four-lane kernel (plan_call);
     // either way c^(P-1) mod P^2 ends in the s74 slots of the unchanged L-function / CRT tail.
@@ -3166,14 +3170,18 @@ static int decrypt_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t cou
     const bool quad = pl.quad, split = pl.split;
     Launch &Lc = pl.main, &Lq = pl.q, &Lp4 = pl.p4, &Lq4 = pl.q4;
     const int S = Lc.S, L = Lc.L, nw = k->n_words, cw = 2 * nw;
-    if (gh && (rc = c->gh[1].ensure((size_t)L * kGhRowWords * 4))) return rc;
     // where chunk [off, off + cnt) leaves its plaintext rows, and their width in words
-    const int mw = gh ? kGhRowWords : nw;
+    const int mw = !gh ? nw : gh->slots ? (gh->slots * gh->slot_words + 3) / 4 * 4 : kGhRowWords;
+    if (gh && (rc = c->gh[1].ensure((size_t)L * mw * 4))) return rc;
     auto m_rows = [&](size_t off) {
         return gh ? (uint32_t *)c->gh[1].p : m_full ? m_full + off * nw : (uint32_t *)nullptr;
     };
     auto gh_decode = [&](size_t off, size_t cnt) {
-        if (gh)
+        if (gh && gh->slots)
+            hipLaunchKernelGGL(k_unpack_gh_slots, dim3((unsigned)((cnt * gh->slots + 255) / 256)), dim3(256), 0,
+                               c->stream, (const uint32_t *)c->gh[1].p, mw, off, cnt, count, gh->bins, gh->slots,
+                               gh->slot_words, gh->g, gh->h, gh->g_code, gh->h_code);
+        else if (gh)
             hipLaunchKernelGGL(k_unpack_gh, Lc.grid(), dim3(256), 0, c->stream, (const uint32_t *)c->gh[1].p,
                                kGhRowWords, cnt, gh->g ? gh->g + off : nullptr, gh->h ? gh->h + off : nullptr,
                                gh->g_code ? gh->g_code + off : nullptr, gh->h_code ? gh->h_code + off : nullptr);
@@ -3325,6 +3333,167 @@ extern "C" int fthe_decrypt_gh_packed_dev(fthe_key *k, fthe_ctx *c, const uint32
                                           float *h, int64_t *g_code, int64_t *h_code, int short_pt) {
     const GhOut o{g, h, g_code, h_code};
     return decrypt_impl(k, c, ct, count, nullptr, nullptr, nullptr, short_pt != 0, &o);
+}
+
+// ---------------------------------------------------------------------------
+// Slot-packed pairs: several (g, h) bins in one ciphertext (include/fthe.h)
+static bool gh_slot_bits_ok(int slot_bits) { return slot_bits >= FTHE_GH_SLOT_BITS_MIN && slot_bits % 32 == 0; }
+
+extern "C" int fthe_gh_slots(const fthe_key *k, int slot_bits, int short_pt) {
+    if (!k || !gh_slot_bits_ok(slot_bits) || (short_pt && !k->priv)) return 0;
+    const size_t B = short_pt ? k->p.bits() : k->n.bits();
+    return B ? (int)((B - 1) / (size_t)slot_bits) : 0;
+}
+
+// the slot count of a call: `slots` itself, or the key's maximum for 0; FTHE_ERR_ARG when the key has no room
+static int gh_slots_of(const fthe_key *k, int slot_bits, int short_pt, int slots, int *out) {
+    const int mx = fthe_gh_slots(k, slot_bits, short_pt);
+    if (mx <= 0 || slots < 0 || slots > mx) return FTHE_ERR_ARG;
+    *out = slots ? slots : mx;
+    return FTHE_OK;
+}
+
+extern "C" int fthe_pack_gh_slots_dev(fthe_ctx *c, const float *g, const float *h, size_t count, int slot_bits,
+                                      int slots, uint32_t *m) {
+    if (!c || ((!g || !h || !m) && count) || !gh_slot_bits_ok(slot_bits) || slots <= 0) return FTHE_ERR_ARG;
+    if ((long long)slots * (slot_bits / 32) > 0x7fffffffLL) return FTHE_ERR_ARG;     // the row width is an int
+    if (!count) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    const size_t rows = (count + slots - 1) / slots;
+    const int sw = slot_bits / 32;
+    hipLaunchKernelGGL(k_pack_gh_slots, grid256(rows * slots), dim3(256), 0, c->stream, g, h, count, rows, slots, sw,
+                       slots * sw, m);
+    return hipGetLastError() == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+}
+
+extern "C" int fthe_unpack_gh_slots_dev(fthe_ctx *c, const uint32_t *m, int stride_words, size_t count, int slot_bits,
+                                        int slots, float *g, float *h, int64_t *g_code, int64_t *h_code) {
+    if (!c || (!m && count) || !gh_slot_bits_ok(slot_bits) || slots <= 0) return FTHE_ERR_ARG;
+    if ((long long)stride_words < (long long)slots * (slot_bits / 32)) return FTHE_ERR_ARG;
+    if (!count) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    const size_t rows = (count + slots - 1) / slots;
+    hipLaunchKernelGGL(k_unpack_gh_slots, grid256(rows * slots), dim3(256), 0, c->stream, m, stride_words, (size_t)0,
+                       rows, rows, count, slots, slot_bits / 32, g, h, g_code, h_code);
+    return hipGetLastError() == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+}
+
+// (g, h) device floats -> rows of slots * slot_words plaintext words in the context's buffer -> the encrypt of
+// general plaintexts, one r per row; `slots` is resolved by the caller.
+static int encrypt_gh_slots_impl(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count, int slot_bits,
+                                 int slots, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out, int flags,
+                                 HostPipe *pipe) {
+    HIPOK(hipSetDevice(c->device));
+    const size_t rows = (count + slots - 1) / slots;
+    const int sw = slot_bits / 32, mww = slots * sw;
+    int rc = c->gh[0].ensure(std::max<size_t>(4, rows * mww * 4));
+    if (rc) return rc;
+    if (count)
+        hipLaunchKernelGGL(k_pack_gh_slots, grid256(rows * slots), dim3(256), 0, c->stream, g, h, count, rows, slots, sw,
+                           mww, (uint32_t *)c->gh[0].p);
+    MsgSrc ms; ms.mw = (const uint32_t *)c->gh[0].p; ms.mww = mww;
+    return encrypt_impl(k, c, ms, rows, r, r_words, rng_seed, out, flags, pipe);
+}
+
+extern "C" int fthe_encrypt_gh_slots_dev(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                         int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed,
+                                         uint32_t *out, int flags, int slots) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    return encrypt_gh_slots_impl(k, c, g, h, count, slot_bits, slots, r, r_words, rng_seed, out, flags, nullptr);
+}
+
+// count = bins; the ciphertext rows are ceil(count / slots)
+static int decrypt_gh_slots_impl(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits, int slots,
+                                 const GhOut &dst, bool short_pt, HostPipe *pipe) {
+    GhOut o = dst;
+    o.slots = slots; o.slot_words = slot_bits / 32; o.bins = count;
+    return decrypt_impl(k, c, ct, (count + slots - 1) / slots, nullptr, nullptr, pipe, short_pt, &o);
+}
+
+static int decrypt_gh_slots_args(const fthe_key *k, const fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits,
+                                 int short_pt, int *slots) {
+    if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
+    if (!k->priv) return FTHE_ERR_NOPRIV;
+    return gh_slots_of(k, slot_bits, short_pt != 0, *slots, slots);
+}
+
+extern "C" int fthe_decrypt_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits,
+                                         float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt,
+                                         int slots) {
+    int rc = decrypt_gh_slots_args(k, c, ct, count, slot_bits, short_pt, &slots);
+    if (rc) return rc;
+    return decrypt_gh_slots_impl(k, c, ct, count, slot_bits, slots, GhOut{g, h, g_code, h_code}, short_pt != 0, nullptr);
+}
+
+// Compress: count pair-packed ciphertexts -> rows = ceil(count / slots) slot-packed ones,
+//     out[i] = prod_j x[j rows + i]^(2^(j slot_bits)) mod n^2,
+// by Horner from the top plane: X = x_top; then per plane below it slot_bits squarings and a product by
+// that plane's row.  A product by a raw row takes X out of the Montgomery domain (X x R^-1), so every step but
+// the last is followed by a product by R^2.  Rows whose top planes run past count (the last rows) start one
+// plane lower instead of multiplying by 1: two programs, for rows [0, nA) with J planes and [nA, rows) with
+// J - 1, uploaded together.  Row I/O where the key has it and the planes fit the row table, else the slot form.
+extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, int slot_bits,
+                                          uint32_t *out, int slots) {
+    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!count) return FTHE_OK;
+    const size_t rows = (count + slots - 1) / slots, cw = 2 * (size_t)k->n_words;
+    const int J = (int)((count + rows - 1) / rows);          // planes of the first nA rows; J - 1 for the rest
+    const size_t nA = count - (size_t)(J - 1) * rows;
+    const bool rowio = k->rowio && J + 1 <= 16;
+    const int base = nslots_for(k);
+    Launch Lc;
+    rc = rowio ? begin_call(c, k, rows, Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
+               : begin_call(c, k, rows, Lc, base + J, k->sn2);
+    if (rc) return rc;
+    const int S = Lc.S, L = Lc.L;
+    auto horner = [&](int planes) {
+        Prog p;
+        p.lds_a = !rowio && lds_prefetch(k->sn2);
+        if (rowio) p.loadw(planes - 1); else p.loadx(base + planes - 1);
+        for (int j = planes - 2; j >= 0; j--) {
+            p.mul(SL_C0);                                     // into Montgomery form
+            if (rowio) { p.sqr(slot_bits); p.mulw(j); } else p.sqr_mul(slot_bits, base + j);
+        }
+        if (rowio) p.storew(planes); else p.storex(SL_OUTP);
+        p.end();
+        return p;
+    };
+    const Prog pa = horner(J), pb = J > 1 ? horner(J - 1) : Prog();
+    Prog both; both.w = pa.w; both.w.insert(both.w.end(), pb.w.begin(), pb.w.end());
+    fthe_key::PH ph;
+    if ((rc = upload_dyn_prog(c, both, ph, c->io[3]))) return rc;
+    HIPOK(hipEventRecord(c->ev0, c->stream));
+    Lc.fill(SL_C0, k->c_R2n2);
+    // rows [r0, r1) of the output, each the Horner form of its `planes` planes
+    auto run = [&](size_t r0, size_t r1, int planes, const Prog &p, const uint32_t *dprog) -> int {
+        if (planes == 1 && r1 > r0)                           // a lone plane is its own slot 0
+            HIPOK(hipMemcpyAsync(out + r0 * cw, x + r0 * cw, (r1 - r0) * cw * 4, hipMemcpyDeviceToDevice, c->stream));
+        for (size_t off = r0; planes > 1 && off < r1; off += L) {
+            const size_t cnt = std::min((size_t)L, r1 - off);
+            Lc.live = cnt;
+            if (rowio) {
+                const void *tab[16];
+                for (int j = 0; j < planes; j++) tab[j] = x + ((size_t)j * rows + off) * cw;
+                tab[planes] = out + off * cw;
+                if (int e = launch_dyn(Lc, dprog, p.montmuls, k->mn2, tab, planes + 1)) return e;
+                continue;
+            }
+            for (int j = 0; j < planes; j++)
+                pack_rows(c->stream, x + ((size_t)j * rows + off) * cw, (int)cw, cnt, 0, Lc.slot(base + j), S, L, Lc.B);
+            if (int e = launch_dyn(Lc, dprog, p.montmuls, k->mn2)) return e;
+            unpack_rows(c->stream, Lc.slot(SL_OUTP), k->cst(k->c_n2), S, L, cnt, out + off * cw, (int)cw, Lc.B);
+        }
+        return FTHE_OK;
+    };
+    const uint32_t *dprog = (const uint32_t *)c->io[3].p;
+    if ((rc = run(0, nA, J, pa, dprog))) return rc;
+    if (J > 1 && (rc = run(nA, rows, J - 1, pb, dprog + pa.w.size()))) return rc;
+    return end_call(c, Lc);
 }
 
 // ---------------------------------------------------------------------------
@@ -4209,6 +4378,73 @@ extern "C" int fthe_decrypt_gh_packed(fthe_key *k, fthe_ctx *c, const uint32_t *
     if (g_code) HIPOK(hipMemcpy(g_code, dgc, count * 8, hipMemcpyDeviceToHost));
     if (h_code) HIPOK(hipMemcpy(h_code, dhc, count * 8, hipMemcpyDeviceToHost));
     return FTHE_OK;
+}
+
+// Host-resident slot-packed pairs: as the packed forms above, with rows = ceil(count / slots) ciphertexts (and
+// injected r) through the pipe and the count floats / codes in one copy each.
+extern "C" int fthe_encrypt_gh_slots(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                     int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out,
+                                     int flags, int slots) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    if (r && (r_words <= 0 || r_words > ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
+                                         : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)))) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t cw = 2 * (size_t)k->n_words, rows = (count + slots - 1) / slots;
+    if ((rc = c->gh[2].ensure(std::max<size_t>(4, count * 8))) || (rc = c->io[2].ensure(std::max<size_t>(4, rows * cw * 4))))
+        return rc;
+    if (r && (rc = c->io[1].ensure(std::max<size_t>(4, rows * r_words * 4)))) return rc;
+    float *dg = (float *)c->gh[2].p, *dh = dg + count;
+    if (count) {
+        HIPOK(hipMemcpyAsync(dg, g, count * 4, hipMemcpyHostToDevice, c->stream));
+        HIPOK(hipMemcpyAsync(dh, h, count * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HostPipe pipe{c};
+    if (r) pipe.add_in(r, c->io[1].p, (size_t)r_words * 4);
+    pipe.add_out(out, c->io[2].p, cw * 4);
+    if ((rc = encrypt_gh_slots_impl(k, c, dg, dh, count, slot_bits, slots, r ? (const uint32_t *)c->io[1].p : nullptr,
+                                    r_words, rng_seed, (uint32_t *)c->io[2].p, flags, count ? &pipe : nullptr)))
+        return rc;
+    return pipe.finish();
+}
+
+extern "C" int fthe_decrypt_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits,
+                                     float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt, int slots) {
+    int rc = decrypt_gh_slots_args(k, c, ct, count, slot_bits, short_pt, &slots);
+    if (rc) return rc;
+    HIPOK(hipSetDevice(c->device));
+    const size_t cw = 2 * (size_t)k->n_words, rows = (count + slots - 1) / slots;
+    // device outputs in one buffer: g codes, h codes, g floats, h floats
+    if ((rc = c->io[0].ensure(std::max<size_t>(4, rows * cw * 4))) || (rc = c->gh[2].ensure(std::max<size_t>(8, count * 24))))
+        return rc;
+    int64_t *dgc = (int64_t *)c->gh[2].p, *dhc = dgc + count;
+    float *dg = (float *)(dhc + count), *dh = dg + count;
+    HostPipe pipe{c};
+    pipe.add_in(ct, c->io[0].p, cw * 4);
+    if ((rc = decrypt_gh_slots_impl(k, c, (const uint32_t *)c->io[0].p, count, slot_bits, slots,
+                                    GhOut{dg, dh, dgc, dhc}, short_pt != 0, count ? &pipe : nullptr))) return rc;
+    if ((rc = pipe.finish())) return rc;
+    if (!count) return FTHE_OK;
+    if (g) HIPOK(hipMemcpy(g, dg, count * 4, hipMemcpyDeviceToHost));
+    if (h) HIPOK(hipMemcpy(h, dh, count * 4, hipMemcpyDeviceToHost));
+    if (g_code) HIPOK(hipMemcpy(g_code, dgc, count * 8, hipMemcpyDeviceToHost));
+    if (h_code) HIPOK(hipMemcpy(h_code, dhc, count * 8, hipMemcpyDeviceToHost));
+    return FTHE_OK;
+}
+
+extern "C" int fthe_compress_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, int slot_bits,
+                                      uint32_t *out, int slots) {
+    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    HIPOK(hipSetDevice(c->device));
+    HostIO io{c}; void *dx, *dout;
+    const size_t row = 2 * (size_t)k->n_words * 4, rows = (count + slots - 1) / slots;
+    if ((rc = io.in(0, x, count * row, &dx))) return rc;
+    if ((rc = io.outbuf(2, rows * row, &dout))) return rc;
+    if ((rc = fthe_compress_gh_slots_dev(k, c, (const uint32_t *)dx, count, slot_bits, (uint32_t *)dout, slots))) return rc;
+    return io.back(out, dout, rows * row);
 }
 
 // Staging buffers of the shared queues above this many bytes are released after their batch

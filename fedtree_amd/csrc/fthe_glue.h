@@ -59,4 +59,9 @@ __global__ void k_decode_fixed(const uint64_t *m, size_t count, float *x);
 __global__ void k_pack_gh(const float *g, const float *h, size_t count, uint32_t *m);
 __global__ void k_unpack_gh(const uint32_t *m, int stride, size_t count, float *g, float *h, int64_t *g_code,
                             int64_t *h_code);
+// slot-packed pairs: several of those plaintexts in one, slot_words apart, bins in plane order
+__global__ void k_pack_gh_slots(const float *g, const float *h, size_t count, size_t rows, int slots, int slot_words,
+                                int row_words, uint32_t *m);
+__global__ void k_unpack_gh_slots(const uint32_t *m, int stride, size_t row0, size_t nrows, size_t rows, size_t count,
+                                  int slots, int slot_words, float *g, float *h, int64_t *g_code, int64_t *h_code);
 }  // namespace fthe

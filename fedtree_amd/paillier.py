@@ -127,6 +127,66 @@ def packed_bits_after(op, bits_a, bits_b=None, k=None):
 
 
 # --------------------------------------------------------------------------
+# Slot-packed pairs (include/fthe.h FTHE_GH_SLOT_*): several packed plaintexts T_j in one,
+# sum_j T_j 2^(j slot_bits), bins in plane order (bin b = slot b // rows of row b % rows).  The numpy
+# statement of the layout; the engine's k_pack_gh_slots / k_unpack_gh_slots are checked against it.
+GH_SLOT_BITS_MIN = 224
+
+
+def _slot_words(slot_bits):
+    slot_bits = int(slot_bits)
+    if slot_bits < GH_SLOT_BITS_MIN or slot_bits % 32:
+        raise ValueError(f"slot_bits {slot_bits}: a multiple of 32, at least {GH_SLOT_BITS_MIN}")
+    return slot_bits // 32
+
+
+def gh_slot_count(key_bits, slot_bits):
+    """Slots of slot_bits bits in a plaintext below a modulus of key_bits bits (bits of n, or of p for the
+    short decrypt): floor((key_bits - 1) / slot_bits), 0 when the key is too small.  slot_bits must be a
+    multiple of 32 of at least GH_SLOT_BITS_MIN."""
+    return max(0, (int(key_bits) - 1) // (32 * _slot_words(slot_bits)))
+
+
+def gh_slot_rows(count, slots):
+    """Ciphertexts that hold count bins, slots to a ciphertext."""
+    return -(-int(count) // int(slots))
+
+
+def pack_gh_slots(words, slot_bits, slots):
+    """(count, w) uint32 plaintext words per bin (pack_gh's six, or up to slot_bits / 32 of a plaintext that
+    has grown) -> (rows, slots * slot_bits / 32) uint32 slot-packed plaintexts in plane order; empty slots
+    and pad words are zero."""
+    sw = _slot_words(slot_bits)
+    w = np.asarray(words, dtype=np.uint32)
+    w = w.reshape(-1, w.shape[-1] if w.ndim > 1 else GH_PACKED_WORDS)
+    if w.shape[1] > sw:
+        raise ValueError(f"pack_gh_slots: {w.shape[1]} words per bin do not fit a slot of {sw}")
+    count, rows = len(w), gh_slot_rows(len(w), slots)
+    planes = np.zeros((int(slots) * rows, sw), dtype=np.uint32)
+    planes[:count, :w.shape[1]] = w
+    # plane j, row i -> row i, words [j sw, (j + 1) sw)
+    return np.ascontiguousarray(planes.reshape(int(slots), rows, sw).transpose(1, 0, 2)).reshape(rows, int(slots) * sw)
+
+
+def split_gh_slots(rows, count, slot_bits, slots):
+    """Slot-packed plaintext rows (their low slots * slot_bits / 32 words) -> (count, slot_bits / 32) uint32,
+    the slot of every bin."""
+    sw = _slot_words(slot_bits)
+    m = np.asarray(rows, dtype=np.uint32)
+    nrows = gh_slot_rows(count, slots)
+    if nrows == 0:
+        return np.zeros((0, sw), dtype=np.uint32)
+    m = m.reshape(nrows, -1)[:, :int(slots) * sw]
+    return np.ascontiguousarray(m.reshape(nrows, int(slots), sw).transpose(1, 0, 2)).reshape(-1, sw)[:int(count)]
+
+
+def unpack_gh_slots(rows, count, slot_bits, slots, codes=False):
+    """Slot-packed plaintext rows -> float (g, h) of the count bins (codes: also the int64 codes): each
+    slot's six low words through unpack_gh."""
+    return unpack_gh(split_gh_slots(rows, count, slot_bits, slots), codes=codes)
+
+
+# --------------------------------------------------------------------------
 class Device:
     """One engine context (HIP stream + workspace) on one GPU.
 
@@ -461,6 +521,65 @@ class Paillier:
                                                    _ptr(hc), int(bool(short))), "decrypt_gh_packed")
         return (g, h, gc, hc) if codes else (g, h)
 
+    # ---- slot-packed pairs: several bins in one ciphertext (include/fthe.h FTHE_GH_SLOT_*) -----
+    def gh_slots(self, slot_bits, short=False):
+        """Slots of slot_bits bits a ciphertext of this key holds (fthe_gh_slots); short: below p, for the
+        short decrypt.  0: none (key too small, bad slot_bits, short on a public key)."""
+        return int(self.lib.fthe_gh_slots(self._key, int(slot_bits), int(bool(short))))
+
+    def _slots_for(self, slot_bits, slots, short=False, what="gh_slots"):
+        mx = self.gh_slots(slot_bits, short)
+        if mx <= 0 or not 0 <= int(slots) <= mx:
+            _lib.check(_lib.FTHE_ERR_ARG, what)
+        return int(slots) or mx
+
+    def encrypt_gh_slots(self, g, h, slot_bits, r=None, seed=0, public=False, fixed_base=False,
+                         fixed_base_exact=False, slots=0):
+        """Enc of the slot-packed plaintexts of (g, h): ceil(count / slots) ciphertexts in plane order
+        (fthe_encrypt_gh_slots).  r: one per ciphertext; seed and the modes as encrypt_u64.  slots: 0 = the
+        key's maximum; a batch meant for the short decrypt needs slots <= gh_slots(slot_bits, short=True)."""
+        g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        if len(g) != len(h):
+            raise ValueError(f"encrypt_gh_slots: {len(g)} g for {len(h)} h")
+        rows = gh_slot_rows(len(g), self._slots_for(slot_bits, slots, what="encrypt_gh_slots"))
+        out = np.zeros((rows, self._cw()), dtype=np.uint32)
+        rw = self._rand_rows(r, rows, public, fixed_base, fixed_base_exact)
+        _lib.check(self.lib.fthe_encrypt_gh_slots(self._key, self.dev.ctx, _ptr(g), _ptr(h), len(g), int(slot_bits),
+                                                  _ptr(rw), rw.shape[1] if rw is not None else 0, int(seed), _ptr(out),
+                                                  self._flags(public, fixed_base, fixed_base_exact), int(slots)),
+                   "encrypt_gh_slots")
+        return out
+
+    def decrypt_gh_slots(self, c, count, slot_bits, short=False, codes=False, slots=0):
+        """Slot-packed ciphertexts holding count bins -> float (g, h) (codes: also the int64 codes), decoded
+        on the device chunk by chunk (fthe_decrypt_gh_slots).  slots: as the batch was built; 0 = the key's
+        maximum for this decrypt form."""
+        c = np.ascontiguousarray(c, dtype=np.uint32).reshape(-1, self._cw())
+        cnt = int(count)
+        if self.has_private:
+            rows = gh_slot_rows(cnt, self._slots_for(slot_bits, slots, short, "decrypt_gh_slots"))
+            if len(c) != rows:
+                raise ValueError(f"decrypt_gh_slots: {len(c)} ciphertexts for {cnt} bins in {rows} rows")
+        g, h = np.zeros(cnt, np.float32), np.zeros(cnt, np.float32)
+        gc = np.zeros(cnt, np.int64) if codes else None
+        hc = np.zeros(cnt, np.int64) if codes else None
+        _lib.check(self.lib.fthe_decrypt_gh_slots(self._key, self.dev.ctx, _ptr(c), cnt, int(slot_bits), _ptr(g),
+                                                  _ptr(h), _ptr(gc), _ptr(hc), int(bool(short)), int(slots)),
+                   "decrypt_gh_slots")
+        return (g, h, gc, hc) if codes else (g, h)
+
+    def compress_gh_slots(self, x, slot_bits, slots=0):
+        """count pair-packed ciphertexts -> ceil(count / slots) slot-packed ones, row i the product of
+        x[j rows + i]^(2^(j slot_bits)) mod n^2 (fthe_compress_gh_slots): every plaintext must be below
+        2^slot_bits."""
+        x = np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, self._cw())
+        rows = gh_slot_rows(len(x), self._slots_for(slot_bits, slots, what="compress_gh_slots"))
+        out = np.zeros((rows, self._cw()), dtype=np.uint32)
+        _lib.check(self.lib.fthe_compress_gh_slots(self._key, self.dev.ctx, _ptr(x), len(x), int(slot_bits), _ptr(out),
+                                                   int(slots)), "compress_gh_slots")
+        return out
+
     def sub_bits_batch(self, a, b, bits=GH_PACKED_BITS):
         """a * b^(2^bits - 1) mod n^2 (fthe_sub_bits): a - b on plaintexts that live mod 2^bits; the
         default is the packed pairs' width, bits = 64 is sub_batch."""
@@ -695,6 +814,55 @@ class Paillier:
             self._dptr(h), self._dptr(g_code), self._dptr(h_code), int(bool(short))), "decrypt_gh_packed_dev")
 
     @_stream_ordered
+    def pack_gh_slots_dev(self, g, h, out, slot_bits, slots):
+        """Device float32 g, h -> device (rows, slots * slot_bits / 32) slot-packed plaintext words."""
+        _lib.check(self.lib.fthe_pack_gh_slots_dev(self.dev.ctx, ctypes.c_void_p(g.data_ptr()),
+                                                   ctypes.c_void_p(h.data_ptr()), g.numel(), int(slot_bits), int(slots),
+                                                   ctypes.c_void_p(out.data_ptr())), "pack_gh_slots_dev")
+        return out
+
+    @_stream_ordered
+    def unpack_gh_slots_dev(self, m, count, slot_bits, slots, g=None, h=None, g_code=None, h_code=None,
+                            stride_words=None):
+        """Device slot-packed plaintext rows stride_words apart (default: slots * slot_bits / 32) -> device
+        float32 g, h and int64 codes of the count bins (each optional)."""
+        if stride_words is None:
+            stride_words = int(slots) * (int(slot_bits) // 32)
+        _lib.check(self.lib.fthe_unpack_gh_slots_dev(self.dev.ctx, ctypes.c_void_p(m.data_ptr()), int(stride_words),
+                                                     int(count), int(slot_bits), int(slots), self._dptr(g),
+                                                     self._dptr(h), self._dptr(g_code), self._dptr(h_code)),
+                   "unpack_gh_slots_dev")
+
+    @_stream_ordered
+    def encrypt_gh_slots_dev(self, g, h, out, slot_bits, r=None, seed=0, public=False, fixed_base=False,
+                             fixed_base_exact=False, slots=0):
+        """Device float32 g, h -> device slot-packed ciphertexts out (rows, 2nw); otherwise as encrypt_gh_slots."""
+        _lib.check(self.lib.fthe_encrypt_gh_slots_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(g.data_ptr()), ctypes.c_void_p(h.data_ptr()), g.numel(),
+            int(slot_bits), self._dptr(r), r.shape[-1] if r is not None else 0, int(seed),
+            ctypes.c_void_p(out.data_ptr()), self._flags(public, fixed_base, fixed_base_exact), int(slots)),
+            "encrypt_gh_slots_dev")
+        return out
+
+    @_stream_ordered
+    def decrypt_gh_slots_dev(self, c, count, slot_bits, g=None, h=None, g_code=None, h_code=None, short=False,
+                             slots=0):
+        """Device slot-packed ciphertexts of count bins -> device float32 g, h and int64 codes (each optional)."""
+        _lib.check(self.lib.fthe_decrypt_gh_slots_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(c.data_ptr()), int(count), int(slot_bits), self._dptr(g),
+            self._dptr(h), self._dptr(g_code), self._dptr(h_code), int(bool(short)), int(slots)),
+            "decrypt_gh_slots_dev")
+
+    @_stream_ordered
+    def compress_gh_slots_dev(self, x, count, slot_bits, out, slots=0):
+        """Device pair-packed ciphertexts x (count, 2nw) -> device slot-packed out (rows, 2nw); out may alias
+        no input."""
+        _lib.check(self.lib.fthe_compress_gh_slots_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()), int(count), int(slot_bits),
+            ctypes.c_void_p(out.data_ptr()), int(slots)), "compress_gh_slots_dev")
+        return out
+
+    @_stream_ordered
     def scan_segments_dev(self, x, seg_ptr, out):
         seg = np.ascontiguousarray(seg_ptr, dtype=np.int64)
         _lib.check(self.lib.fthe_scan_segments_dev(self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()), _ptr(seg),
@@ -827,7 +995,13 @@ class GHPairs:
 
     packed=True (opt-in, include/fthe.h FTHE_GH_*): one ciphertext per pair -- g_enc holds the packed
     ciphertexts and h_enc is None.  pt_bits is then an upper bound on the bits of the plaintexts
-    (packed_bits_after), checked against the key before a decrypt."""
+    (packed_bits_after), checked against the key before a decrypt.
+
+    slot_bits > 0 (include/fthe.h FTHE_GH_SLOT_*): a packed batch whose len(self) bins lie `slots` to a
+    ciphertext in slots of slot_bits bits, in plane order -- g_enc holds ceil(len / slots) rows, from
+    homo_encrypt(slot_bits=...) or compress().  pt_bits then bounds every slot's content and must stay
+    within slot_bits: such batches add (and merge by reduce_kway) but do not subtract or enter the
+    histogram methods; subtract first, compress after."""
 
     def __init__(self, g, h=None, paillier=None, packed=False):
         self.g = np.ascontiguousarray(g, dtype=np.float32).copy()
@@ -837,19 +1011,41 @@ class GHPairs:
         self.paillier = paillier
         self.packed = bool(packed)
         self.pt_bits = 0
+        self.slot_bits = self.slots = 0
 
     def __len__(self):
         return len(self.g)
 
-    def homo_encrypt(self, pl, r_g=None, r_h=None, seed=0, fixed_base_exact=False):
+    @staticmethod
+    def _slots_in(pl, slot_bits, slots=0, short=False):
+        """Slot count of a batch under pl's key (slots, or the key's maximum for 0); ValueError when the key
+        holds none, or fewer than asked."""
+        room = pl.p.bit_length() if short else pl.modulus.bit_length()
+        mx = gh_slot_count(room, slot_bits)
+        if mx == 0 or not 0 <= int(slots) <= mx:
+            raise ValueError(f"{int(slots) or 1} slot(s) of {slot_bits} bits do not fit below "
+                             f"{'p' if short else 'n'} ({room} bits)")
+        return int(slots) or mx
+
+    def homo_encrypt(self, pl, r_g=None, r_h=None, seed=0, fixed_base_exact=False, slot_bits=0, slots=0):
         """GHPair::homo_encrypt (common.h:125-134): encrypt g,h, zero them, set encrypted.
         fixed_base_exact: the table-driven randomizer (key holder: same distribution; public
-        key with published bases: within 2^-62 of it; otherwise the default path)."""
+        key with published bases: within 2^-62 of it; otherwise the default path).
+        slot_bits (packed batches only): slot-packed, `slots` bins to a ciphertext (0: the key's maximum;
+        r_g then holds one r per ciphertext row)."""
         if self.encrypted:
             return self
+        if slot_bits and not self.packed:
+            raise ValueError("GHPairs: slot_bits needs a packed batch (packed=True)")
         if self.packed:
             fbx = fixed_base_exact and r_g is None and (pl.has_private or pl.has_public_bases)
-            self.g_enc = pl.encrypt_gh_packed(self.g, self.h, r=r_g, seed=seed, fixed_base_exact=fbx)
+            if slot_bits:
+                self.slots = self._slots_in(pl, slot_bits, slots)
+                self.slot_bits = int(slot_bits)
+                self.g_enc = pl.encrypt_gh_slots(self.g, self.h, slot_bits, r=r_g, seed=seed, fixed_base_exact=fbx,
+                                                 slots=self.slots)
+            else:
+                self.g_enc = pl.encrypt_gh_packed(self.g, self.h, r=r_g, seed=seed, fixed_base_exact=fbx)
             self.h_enc = None
             self.pt_bits = GH_PACKED_BITS
             self.paillier = pl
@@ -885,7 +1081,14 @@ class GHPairs:
             if self.pt_bits >= room:
                 raise ValueError(f"packed plaintexts of up to {self.pt_bits} bits do not fit below "
                                  f"{'p' if short else 'n'} ({room} bits): pt_bits must stay under it")
-            self.g, self.h = pl.decrypt_gh_packed(self.g_enc, short=short)
+            if self.slot_bits:
+                if self.pt_bits > self.slot_bits or self.slots * self.slot_bits >= room:
+                    raise ValueError(f"{self.slots} slots of {self.slot_bits} bits (contents up to {self.pt_bits} "
+                                     f"bits) do not fit below {'p' if short else 'n'} ({room} bits)")
+                self.g, self.h = pl.decrypt_gh_slots(self.g_enc, len(self), self.slot_bits, short=short,
+                                                     slots=self.slots)
+            else:
+                self.g, self.h = pl.decrypt_gh_packed(self.g_enc, short=short)
             self.encrypted = False
             return self
         dec = pl.decrypt_u64_shared if shared else pl.decrypt_u64
@@ -905,14 +1108,51 @@ class GHPairs:
             raise ValueError("GHPairs: one operand is packed (one ciphertext per pair), the other is not")
         return self.packed if self.encrypted else rhs.packed
 
-    def _packed_result(self, pl, rows, pt_bits):
-        res = GHPairs(np.zeros(len(rows), np.float32), np.zeros(len(rows), np.float32), pl, packed=True)
+    def _packed_result(self, pl, rows, pt_bits, count=None, slot_bits=0, slots=0):
+        n = len(rows) if count is None else count
+        res = GHPairs(np.zeros(n, np.float32), np.zeros(n, np.float32), pl, packed=True)
         res.g_enc, res.pt_bits, res.encrypted = rows, pt_bits, True
+        res.slot_bits, res.slots = slot_bits, slots
         return res
+
+    def _no_slots(self, what):
+        if self.slot_bits:
+            raise ValueError(f"GHPairs: {what} is not defined on slot-packed ciphertexts "
+                             "(subtract and build histograms first, compress after)")
+
+    def compress(self, slot_bits=None, slots=0):
+        """An encrypted packed batch -> the slot-packed batch of the same bins (Paillier.compress_gh_slots).
+        slot_bits: default the smallest multiple of 32 that is >= max(pt_bits, GH_SLOT_BITS_MIN); ValueError
+        when it is below pt_bits or leaves the key no slot."""
+        if not (self.encrypted and self.packed) or self.slot_bits:
+            raise ValueError("GHPairs.compress: needs an encrypted pair-packed batch")
+        if slot_bits is None:
+            slot_bits = (max(self.pt_bits, GH_SLOT_BITS_MIN) + 31) // 32 * 32
+        if _slot_words(slot_bits) * 32 < self.pt_bits:
+            raise ValueError(f"GHPairs.compress: plaintexts of up to {self.pt_bits} bits do not fit slots of "
+                             f"{slot_bits}")
+        pl = self.paillier
+        slots = self._slots_in(pl, slot_bits, slots)
+        return self._packed_result(pl, pl.compress_gh_slots(self.g_enc, slot_bits, slots=slots), self.pt_bits,
+                                   len(self), int(slot_bits), slots)
+
+    def _add_slots(self, rhs):
+        if not (self.encrypted and rhs.encrypted and self.slot_bits and rhs.slot_bits):
+            raise ValueError("GHPairs: a slot-packed batch adds only to an encrypted slot-packed batch")
+        if (len(self), self.slot_bits, self.slots) != (len(rhs), rhs.slot_bits, rhs.slots):
+            raise ValueError("GHPairs: slot-packed operands differ in length, slot_bits or slots")
+        bits = packed_bits_after("add", self.pt_bits, rhs.pt_bits)
+        if bits > self.slot_bits:
+            raise ValueError(f"GHPairs: the sum may reach {bits} bits, above the slots' {self.slot_bits}")
+        pl = self.paillier
+        return self._packed_result(pl, pl.add_batch(self.g_enc, rhs.g_enc), bits, len(self), self.slot_bits,
+                                   self.slots)
 
     def __add__(self, rhs):
         """GHPair::operator+ (common.h:150-195).  An unencrypted side is first
         encrypted with a fresh r."""
+        if self.slot_bits or rhs.slot_bits:
+            return self._add_slots(rhs)
         if not self.encrypted and not rhs.encrypted:
             return GHPairs(self.g + rhs.g, self.h + rhs.h)
         pl = rhs.paillier if not self.encrypted else self.paillier
@@ -931,6 +1171,8 @@ class GHPairs:
     def __sub__(self, rhs):
         """GHPair::operator- (common.h:253-337): rhs^(2^64-1) then add; an
         unencrypted rhs is negated and encrypted."""
+        self._no_slots("-")
+        rhs._no_slots("-")
         if not self.encrypted and not rhs.encrypted:
             return GHPairs(self.g - rhs.g, self.h - rhs.h)
         if not rhs.encrypted:
@@ -1015,9 +1257,10 @@ class HEParty:
     def __init__(self, paillier=None):
         self.paillier = paillier
 
-    def encrypt_histogram(self, hist, seed=0, fixed_base_exact=False):
-        """party.h:118-142.  fixed_base_exact: the published-bases randomizer (send_key(bases=True))."""
-        return hist.homo_encrypt(self.paillier, seed=seed, fixed_base_exact=fixed_base_exact)
+    def encrypt_histogram(self, hist, seed=0, fixed_base_exact=False, slot_bits=0):
+        """party.h:118-142.  fixed_base_exact: the published-bases randomizer (send_key(bases=True)).
+        slot_bits (a packed histogram): slot-packed, the key's maximum of bins to a ciphertext."""
+        return hist.homo_encrypt(self.paillier, seed=seed, fixed_base_exact=fixed_base_exact, slot_bits=slot_bits)
 
     def compute_histogram(self, gh, bin_ids, cut_col_ptr, max_num_bin):
         """Histogram of one node (hist_tree_builder.cpp:565-595, n_nodes_in_level == 1):
@@ -1030,6 +1273,7 @@ class HEParty:
         common.h:156-160 -- same plaintext, different randomness).
         Plain gh: float32 accumulation in instance order (dest.g += src.g).
         Packed gh: the same product over one plane; an empty bin, the ciphertext 1, decodes to (0, 0)."""
+        gh._no_slots("compute_histogram")
         seg_ptr, idx = histogram_segments(bin_ids, cut_col_ptr, max_num_bin)
         n_bins = len(seg_ptr) - 1
         if not gh.encrypted:
@@ -1062,6 +1306,7 @@ class HEParty:
         segmented scan on the device for g and h together.  (An untouched bin
         enters as the ciphertext 1; the reference would promote its zero with a
         fresh Enc(0) -- same plaintexts.)"""
+        hist._no_slots("prefix_histogram")
         cut = np.asarray(cut_col_ptr, dtype=np.int64)
         n_bins = int(cut[-1])
         if not hist.encrypted:
@@ -1158,7 +1403,8 @@ def _ct_from_decimal_dev(dev, buf, offs, words):
 
 
 def wire_encode(g, h=None):
-    """Binary "FTHW" frame of raw little-endian words."""
+    """Binary "FTHW" frame of raw little-endian words.  Packed and slot-packed
+    batches go as their g_enc rows, as they are (h None)."""
     lib = _lib.load()
     g = np.ascontiguousarray(g, dtype=np.uint32)
     cnt, words = g.shape

@@ -492,6 +492,56 @@ int fthe_sub_bits_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uin
 int fthe_sub_bits(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
                   int bits, uint32_t *out);
 
+/* ---- slot-packed pairs: several (g, h) bins in one ciphertext (opt-in; not in the reference) ----
+ * A pair-packed ciphertext (above) uses W = 192 plaintext bits of a key's thousands.  A slot-packed
+ * one holds `slots` such plaintexts T_j, each in a slot of slot_bits bits:
+ *     plaintext = sum_j T_j * 2^(j * slot_bits).
+ * A slot keeps its T_j intact, the residue m_b 2^W of a subtraction included, while T_j < 2^slot_bits
+ * (the caller's bound, as the growth rule above), and decodes by the packed rule, T_j mod 2^W.
+ *   slot_bits   a multiple of 32, at least FTHE_GH_SLOT_BITS_MIN (W + 32: any 2^32 fresh addends);
+ *               slot_words = slot_bits / 32.  Anything else: FTHE_ERR_ARG.
+ *   fthe_gh_slots(key, slot_bits, short_pt) = floor((B - 1) / slot_bits), B = bits(n), or bits(p)
+ *               for the short decrypt: the whole plaintext stays below 2^(B-1).  0: no room (bad
+ *               slot_bits, key too small, short_pt on a public key).
+ *   plane order: count bins go into rows = ceil(count / slots) ciphertexts; bin b is slot b / rows of
+ *               ciphertext b % rows (fthe_reduce_kway's x[j * rows + i]).  A slot whose bin is
+ *               >= count is zero (the factor 1 on the ciphertext side); pad words are zero.
+ * The trailing `slots` argument of the key calls: 0 = the key's maximum (fthe_gh_slots with the call's
+ * own short_pt; the full form for encrypt and compress), else that many (above the maximum:
+ * FTHE_ERR_ARG).  A layout that will be decrypted short must be built with slots <=
+ * fthe_gh_slots(key, slot_bits, 1) and decrypted with the same slots value.
+ * fthe_pack_gh_slots_dev     m: rows x (slots * slot_words) words.
+ * fthe_unpack_gh_slots_dev   rows stride_words (>= slots * slot_words) apart; outputs count each, nullable.
+ * fthe_encrypt_gh_slots      pack, then the encrypt of general plaintexts: r (one per row), r_words,
+ *                      rng_seed and flags as fthe_encrypt_u64.  c: rows * 2*n_words words.
+ * fthe_decrypt_gh_slots      count = bins; c: rows ciphertexts.  Decoded chunk by chunk (no
+ *                      rows x n_words plaintext array).  Public key: FTHE_ERR_NOPRIV.
+ * fthe_compress_gh_slots     x: count pair-packed ciphertexts -> out: rows slot-packed ones,
+ *                      out[i] = prod_j x[j*rows + i]^(2^(j*slot_bits)) mod n^2 (Horner: about
+ *                      slot_bits + 2 products mod n^2 per slot above the lowest).  x rows canonical
+ *                      (< n^2); out may alias no input.  Add and fthe_reduce_kway work on slot-packed
+ *                      ciphertexts of one layout as they are; subtraction does not. */
+#define FTHE_GH_SLOT_BITS_MIN 224
+int fthe_gh_slots(const fthe_key *key, int slot_bits, int short_pt);
+int fthe_pack_gh_slots_dev(fthe_ctx *ctx, const float *g, const float *h, size_t count, int slot_bits,
+                           int slots, uint32_t *m);
+int fthe_unpack_gh_slots_dev(fthe_ctx *ctx, const uint32_t *m, int stride_words, size_t count, int slot_bits,
+                             int slots, float *g, float *h, int64_t *g_code, int64_t *h_code);
+int fthe_encrypt_gh_slots_dev(fthe_key *key, fthe_ctx *ctx, const float *g, const float *h, size_t count,
+                              int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed,
+                              uint32_t *c, int flags, int slots);
+int fthe_encrypt_gh_slots(fthe_key *key, fthe_ctx *ctx, const float *g, const float *h, size_t count,
+                          int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed,
+                          uint32_t *c, int flags, int slots);
+int fthe_decrypt_gh_slots_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *c, size_t count, int slot_bits,
+                              float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt, int slots);
+int fthe_decrypt_gh_slots(fthe_key *key, fthe_ctx *ctx, const uint32_t *c, size_t count, int slot_bits,
+                          float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt, int slots);
+int fthe_compress_gh_slots_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t count, int slot_bits,
+                               uint32_t *out, int slots);
+int fthe_compress_gh_slots(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t count, int slot_bits,
+                           uint32_t *out, int slots);
+
 /* ---- test hook: the randomness of the direct-y CRT encrypt ----------------
  * A key holder's fthe_encrypt_u64[_dev] with r == NULL draws, per ciphertext,
  * y_p uniform in [1, p) and y_q uniform in [1, q) and computes
