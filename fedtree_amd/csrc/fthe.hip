@@ -3545,16 +3545,48 @@ extern "C" int fthe_debug_addb_image(const uint32_t *n, int n_words, uint8_t *ou
     return FTHE_OK;
 }
 
+// The op programs that the two test hooks below admit: pairs (op, argument) up to an END inside prog_words, of
+// LOADX / STOREX / MUL slot (below nslots), SQR count (1..64) and, padic: LOADP / STOREP slot, else CANON.  No
+// other op: the table ops address memory by lane data, the row ops through the kernarg row table.
+static bool debug_prog_ok(const uint32_t *prog, int prog_words, int nslots, bool padic, double *products) {
+    *products = 0;                                         // per lane, as Prog counts them (profiling, roofline)
+    for (int i = 0; i + 1 < prog_words; i += 2) {
+        const uint32_t op = prog[i], a = prog[i + 1];
+        switch (op) {
+        case OP_END: return true;
+        case OP_LOADX: case OP_STOREX: case OP_MUL:
+            if (a >= (uint32_t)nslots) return false;
+            if (op == OP_MUL) *products += 1;
+            break;
+        case OP_SQR:
+            if (a < 1 || a > 64) return false;
+            *products += a;
+            break;
+        case OP_LOADP: case OP_STOREP:
+            if (!padic || a >= (uint32_t)nslots) return false;
+            break;
+        case OP_CANON:
+            if (padic) return false;
+            break;
+        default: return false;
+        }
+    }
+    return false;
+}
+
 // Bring-up / test hook of fthe_nadic_b76: run an op program (uint32 pairs, gen_nadicb.py ops; prog_words words) on
 // the key's matrix-core Barrett n-adic kernel over `count` ciphertexts whose slots 0 .. nslots-1 are given as
 // host limbs (in: nslots x count x 152 limbs of 27 bits: digit x0 in limbs 0..75, x1 in 76..151); slot out_slot
-// is returned the same way.  FTHE_ERR_UNSUPPORTED unless the key runs fthe_nadic_b76.
+// is returned the same way.  FTHE_ERR_UNSUPPORTED unless the key runs fthe_nadic_b76; FTHE_ERR_ARG for a program
+// outside debug_prog_ok, before anything is launched.
 extern "C" int fthe_debug_nadicb_prog(fthe_key *k, fthe_ctx *c, const uint32_t *prog, int prog_words,
                                       const uint32_t *in, int nslots, size_t count, int out_slot, uint32_t *out) {
     if (!k || !c || !prog || prog_words < 2 || !in || nslots <= 0 || nslots > 16 || !count || !out ||
         out_slot < 0 || out_slot >= nslots)
         return FTHE_ERR_ARG;
     if (!k->nadic_b) return FTHE_ERR_UNSUPPORTED;
+    double mm;
+    if (!debug_prog_ok(prog, prog_words, nslots, false, &mm)) return FTHE_ERR_ARG;
     Launch Lc;
     int rc = begin_call(c, k, count, Lc, nslots, k->sn2);
     if (rc) return rc;
@@ -3570,7 +3602,50 @@ extern "C" int fthe_debug_nadicb_prog(fthe_key *k, fthe_ctx *c, const uint32_t *
     fthe_key::PH ph;
     if ((rc = upload_dyn_prog(c, p, ph, c->io[3]))) return rc;
     Lc.live = count;
-    if ((rc = launch_dyn(Lc, c->io[3].p, 0, k->mnB))) return rc;
+    if ((rc = launch_dyn(Lc, c->io[3].p, mm, k->mnB))) return rc;
+    HIPOK(hipStreamSynchronize(c->stream));
+    HIPOK(hipMemcpy(slab.data(), Lc.slot(out_slot), (size_t)S * L * 4, hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < count; g++)
+        for (int j = 0; j < S; j++) out[g * S + j] = slab[(size_t)j * L + g];
+    return end_call(c, Lc);
+}
+
+// The same for the key holder's K = 37 P-adic kernel (side 0: the p context, 1: q's), launched as the key's own
+// exponentiation programs are (table_free): fthe_padic_m37l / m37s / m37t / m37 as the key chose at set-up, or
+// fthe_padic_k37 under FTHE_NO_PADIC_MFMA.  in: nslots x count x 74 limbs of 28 bits (a digit pair: x0 in limbs
+// 0..36, x1 in 37..73; LOADP / STOREP: a plain value in all 74).  FTHE_ERR_UNSUPPORTED unless the key runs that
+// kernel on the CRT region's own slots (not the K = 19 kernel of Paillier-1024).
+extern "C" int fthe_debug_padic_prog(fthe_key *k, fthe_ctx *c, int side, const uint32_t *prog, int prog_words,
+                                     const uint32_t *in, int nslots, size_t count, int out_slot, uint32_t *out) {
+    if (!k || !c || side < 0 || side > 1 || !prog || prog_words < 2 || !in || nslots <= 0 || nslots > 16 || !count ||
+        !out || out_slot < 0 || out_slot >= nslots)
+        return FTHE_ERR_ARG;
+    if (!k->priv) return FTHE_ERR_NOPRIV;
+    const DevMod &mod = side ? k->mqA : k->mpA;
+    if (!k->padic || k->padic_own_slots || mod.kernel_S != 1000 + kPadicK || mod.m.S != k->spq.S)
+        return FTHE_ERR_UNSUPPORTED;
+    double mm;
+    if (!debug_prog_ok(prog, prog_words, nslots, true, &mm)) return FTHE_ERR_ARG;
+    Launch Lc;
+    int rc = begin_call(c, k, count, Lc, nslots, k->spq);
+    if (rc) return rc;
+    if (count > (size_t)Lc.L) return FTHE_ERR_ARG;
+    const int S = Lc.S, L = Lc.L;
+    std::vector<uint32_t> slab((size_t)nslots * S * L, 0u);
+    for (int s = 0; s < nslots; s++)
+        for (size_t g = 0; g < count; g++)
+            for (int j = 0; j < S; j++) slab[((size_t)s * S + j) * L + g] = in[((size_t)s * count + g) * S + j];
+    HIPOK(hipMemcpy(Lc.base, slab.data(), slab.size() * 4, hipMemcpyHostToDevice));
+    Prog p;
+    p.w.assign(prog, prog + prog_words);
+    fthe_key::PH ph;
+    if ((rc = upload_dyn_prog(c, p, ph, c->io[3]))) return rc;
+    Lc.live = count;
+    // its products are counted like any program's: a launch of 64 or more per lane shows under the body's
+    // profiling variant id (fthe_prof_variant), which is how a test tells which body ran
+    if ((rc = launch_montprog(c, Lc.base, S, L, c->io[3].p, mod, mm, count, nullptr, 0, nullptr, false, -1, -1, true)))
+        return rc;
+    Lc.mm += mm * (double)count;
     HIPOK(hipStreamSynchronize(c->stream));
     HIPOK(hipMemcpy(slab.data(), Lc.slot(out_slot), (size_t)S * L * 4, hipMemcpyDeviceToHost));
     for (size_t g = 0; g < count; g++)

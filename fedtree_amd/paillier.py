@@ -363,6 +363,26 @@ class Paillier:
             pub.set_public_bases(bases)
         return pub
 
+    # ---- test hooks: op programs on host-given limbs ---------------------
+    def _debug_prog(self, what, call, prog, slots, out_slot):
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        prog = np.ascontiguousarray(prog, dtype=np.uint32)
+        nslots, count, S = slots.shape
+        out = np.zeros((count, S), dtype=np.uint32)
+        _lib.check(call(_ptr(prog), len(prog), _ptr(slots), nslots, count, int(out_slot), _ptr(out)), what)
+        return out
+
+    def debug_padic_prog(self, side, prog, slots, out_slot):
+        """fthe_debug_padic_prog: the op program `prog` on the key's K = 37 P-adic kernel (side 0: p, 1: q) over
+        slots[nslots][count][74] limbs of 28 bits; the limbs of slot out_slot."""
+        return self._debug_prog("debug_padic_prog", lambda *a: self.lib.fthe_debug_padic_prog(
+            self._key, self.dev.ctx, int(side), *a), prog, slots, out_slot)
+
+    def debug_nadicb_prog(self, prog, slots, out_slot):
+        """fthe_debug_nadicb_prog: the same on fthe_nadic_b76, slots[nslots][count][152] limbs of 27 bits."""
+        return self._debug_prog("debug_nadicb_prog", lambda *a: self.lib.fthe_debug_nadicb_prog(
+            self._key, self.dev.ctx, *a), prog, slots, out_slot)
+
     @property
     def has_private(self):
         return bool(self._key) and bool(self.lib.fthe_key_has_private(self._key))

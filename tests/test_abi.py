@@ -63,6 +63,8 @@ def test_null_arguments_rejected():
     assert lib.fthe_add_dev(None, None, None, None, 0, None) == _lib.FTHE_ERR_ARG
     assert lib.fthe_reduce_segments_dev(None, None, None, 0, None, None, 0, None) == _lib.FTHE_ERR_ARG
     assert lib.fthe_reduce_segments(None, None, None, 0, None, None, 0, None) == _lib.FTHE_ERR_ARG
+    assert lib.fthe_debug_padic_prog(None, None, 0, None, 0, None, 0, 0, 0, None) == _lib.FTHE_ERR_ARG
+    assert lib.fthe_debug_nadicb_prog(None, None, None, 0, None, 0, 0, 0, None) == _lib.FTHE_ERR_ARG
     assert lib.fthe_key_n_words(None) == 0
 
 

@@ -70,3 +70,58 @@ def test_zero_counts_are_no_ops(env):
     assert pl.encrypt_u64(np.zeros(0, np.uint64), fixed_base_exact=True).shape == (0, cw)
     m = np.arange(3, dtype=np.uint64)
     assert np.array_equal(pl.decrypt_u64(pl.encrypt_u64(m, seed=4)), m)
+
+
+def _hook_rejections(call, ok_prog, bad_op_list, extra_ops):
+    """what both op-program hooks refuse before anything is launched: ops outside their list (the table ops 14-17
+    among them, which address memory by lane data), slots at or above nslots, SQR counts outside 1..64, a program
+    without an END inside prog_words, null pointers, bad slots and counts"""
+    E = _lib.FTHE_ERR_ARG
+    assert call(ok_prog) == 0
+    for op in bad_op_list:
+        assert call([1, 0, op, 0, 2, 1, 0, 0]) == E, op
+    assert call([1, 2, 2, 1, 0, 0]) == E and call([1, 0, 2, 2, 0, 0]) == E and call([1, 0, 4, 2, 2, 1, 0, 0]) == E
+    assert call([1, 0xFFFFFFFF, 2, 1, 0, 0]) == E
+    assert call([1, 0, 3, 0, 2, 1, 0, 0]) == E and call([1, 0, 3, 65, 2, 1, 0, 0]) == E
+    assert call([1, 0, 3, 64, 2, 1, 0, 0]) == 0
+    assert call([1, 0, 2, 1]) == E and call([1, 0, 2, 1, 0]) == E and call([1, 0, 2, 1, 3]) == E
+    assert call([1, 0, 2, 1, 0, 0], out_slot=2) == E and call([1, 0, 2, 1, 0, 0], out_slot=-1) == E
+    assert call([1, 0, 2, 1, 0, 0], count=0) == E and call([1, 0, 2, 1, 0, 0], nslots=17) == E
+    assert call([1, 0, 2, 1, 0, 0], nslots=0) == E
+    assert call(None) == E and call([1, 0, 2, 1, 0, 0], slots=None) == E and call([1, 0, 2, 1, 0, 0], out=None) == E
+    for op in extra_ops:
+        assert call([1, 0, op, 0, 2, 1, 0, 0]) == 0, op
+    assert call(ok_prog) == 0                                    # the context still works
+
+
+def test_debug_prog_hooks_validate_their_programs(env):
+    from fedtree_amd.paillier import Paillier
+    dev, pl, pub = env
+    lib, ctx = dev.lib, dev.ctx
+    big = Paillier(dev).keygen(2048, seed=5)
+    E = _lib
+
+    def caller(fn, key, S, *lead):
+        def call(words, nslots=2, out_slot=1, count=4, slots=0, out=0):
+            w = np.array(words, dtype=np.uint32) if words is not None else None
+            sl = np.zeros((max(nslots, 1), 4, S), np.uint32) if slots == 0 else None
+            o = np.zeros((4, S), np.uint32) if out == 0 else None
+            return fn(key, ctx, *lead, _p(w), len(w) if w is not None else 6, _p(sl), nslots, count, out_slot, _p(o))
+        return call
+    other = [5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 21, 24, 0x80000001]
+    for side in (0, 1):
+        _hook_rejections(caller(lib.fthe_debug_padic_prog, big._key, 74, side), [22, 0, 23, 1, 0, 0], other + [20], [])
+    assert caller(lib.fthe_debug_padic_prog, big._key, 74, 2)([1, 0, 2, 1, 0, 0]) == E.FTHE_ERR_ARG       # side
+    assert caller(lib.fthe_debug_padic_prog, big._key, 74, 0)([22, 2, 23, 1, 0, 0]) == E.FTHE_ERR_ARG
+    assert caller(lib.fthe_debug_padic_prog, big._key, 74, 0)([22, 0, 23, 2, 0, 0]) == E.FTHE_ERR_ARG
+    _hook_rejections(caller(lib.fthe_debug_nadicb_prog, big._key, 152), [1, 0, 20, 0, 2, 1, 0, 0], other + [22, 23], [20])
+    ok = [1, 0, 2, 1, 0, 0]
+    # a public key has no P-adic contexts; Paillier-1024 runs the K = 19 kernel, and its n is no b76 modulus
+    assert caller(lib.fthe_debug_padic_prog, big.public()._key, 74, 0)(ok) == E.FTHE_ERR_NOPRIV
+    assert caller(lib.fthe_debug_padic_prog, pub._key, 74, 0)(ok) == E.FTHE_ERR_NOPRIV
+    assert caller(lib.fthe_debug_padic_prog, pl._key, 74, 0)(ok) == E.FTHE_ERR_UNSUPPORTED
+    assert caller(lib.fthe_debug_nadicb_prog, pl._key, 152)(ok) == E.FTHE_ERR_UNSUPPORTED
+    assert caller(lib.fthe_debug_padic_prog, None, 74, 0)(ok) == E.FTHE_ERR_ARG
+    assert caller(lib.fthe_debug_nadicb_prog, None, 152)(ok) == E.FTHE_ERR_ARG
+    m = np.arange(8, dtype=np.uint64)
+    assert np.array_equal(big.decrypt_u64(big.encrypt_u64(m, seed=1)), m)

@@ -771,7 +771,7 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1, dbg=""):
     for j in range(76):
         ctx[gb.N_OFF + 4 * j:gb.N_OFF + 4 * j + 4] = ((n >> (B * j)) & ((1 << B) - 1)).to_bytes(4, 'little')
     rs = [rng.randrange(n) for _ in range(L)]
-    rs[:3] = [0, 1, n - 1]
+    rs[:3] = _cases().nadicb_emu_values(n)                        # 0, 1, n - 1
     IN, T, U, OUT = 0, 1, 2, 3
     slots = bytearray(4 * S * L * 4)
     for g_, r in enumerate(rs):
@@ -802,6 +802,13 @@ def nadicb_selftest(seed=1, bits=2048, count=16, waves=1, batches=1, dbg=""):
                 print(f"  ciphertext {g_}: x0 {x0:#x}\n  x1 {x1:#x}\n  want {want:#x}")
     print(f"nadic_b76: {count} ciphertexts, {bad} mismatches, {steps} wave-instructions emulated")
     return bad
+
+
+def _cases():
+    """the crafted cases shared with the CPU model tests and the GPU tests (tools/barrett_cases.py)"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import barrett_cases
+    return barrett_cases
 
 
 def _m37_asm(variant, ab):
@@ -848,7 +855,7 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None, ju
     lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
     ctx = _m37_ctx(gm, mm, P, s1_lo, variant)
     xs = [rng.randrange(P2) for _ in range(L)]
-    xs[:5] = [0, 1, P - 1, P, P2 - 1]
+    xs[:5] = _cases().padic_emu_values(P)                         # 0, 1, P - 1, P, P^2 - 1
     xs[5:5 + len(extra)] = [x % P2 for x in extra]
     IN, TAB, OUT = 0, 1, 2
     slots = bytearray(3 * S * L * 4)
@@ -888,7 +895,8 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
     cross term at the extremes the kernel admits -- every limb < 2^28 and each digit < 5P (m37t: < 3P, its
     contract), incl. digits whose low 36 limbs are all 2^28 - 1 (the largest Karatsuba half sums and column
     sums), zero halves, one-limb digits and random ones -- against (x0 + x1 P)^4 mod P^2 in Python integers.
-    P: the modulus (default: random of `bits` bits); pairs0: digit pairs that take the first lanes."""
+    P: the modulus (default: random of `bits` bits); pairs0: digit pairs that take the first lanes.  The crafted pairs
+    are barrett_cases.padic_emu_pairs; pairs0 = barrett_cases.padic_edge_pairs runs the rest of the GPU tests' list."""
     asm, gm, s1_lo = _m37_asm(variant, ab)
     import padic_mfma_model as mm
     rng = random.Random(seed)
@@ -899,13 +907,7 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
     MASK = (1 << B) - 1
     nd = mm.TOPEST_DIGIT if variant != 'm37' else 5
     top = nd * P - 1                                             # the largest digit
-    allones = (1 << (B * (K - 1))) - 1                           # limbs 0..35 = 2^28 - 1
-    big = allones + (((top - allones) >> (B * (K - 1))) << (B * (K - 1)))
-    assert big <= top
-    low19 = (1 << (B * 19)) - 1                                  # xL all ones, xH 0
-    high18 = big - (big & low19)                                 # xL 0, xH max
-    special = [big, 0, 1, low19, high18, top, P - 1, (1 << (B * 19)), MASK, big ^ (MASK << (B * 18))]
-    pairs = (list(pairs0) + [(a, b) for a in special for b in special])[:max(40, len(pairs0))]
+    pairs = _cases().padic_emu_pairs(P, variant, pairs0)         # pairs0, then the special digits' pairs, 40 in all
     assert len(pairs) <= 64 and all(0 <= a <= top and 0 <= b <= top for a, b in pairs)
     while len(pairs) < 64:
         pairs.append((rng.randrange(nd * P), rng.randrange(nd * P)))
