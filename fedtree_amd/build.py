@@ -46,6 +46,7 @@ def build_kernels():
             os.environ.pop(k)
             sys.stderr.write(f"build.py: ignoring {k} (A/B generator switch) for the in-tree library\n")
     m37_ab = os.environ.get("FTHE_GEN_M37_AB", "")
+    m37k_ab = os.environ.get("FTHE_GEN_M37K_AB", m37_ab)      # fthe_padic_m37k also knows switches of its own
     addb_dbg = os.environ.get("FTHE_GEN_ADDB_DBG", "")
     nadicb_dbg = os.environ.get("FTHE_GEN_NADICB_DBG", "")
     import gen_montprog  # noqa: E402
@@ -72,10 +73,11 @@ def build_kernels():
                         lambda K=K: gen_padic.gen_padic(K, 28, f"fthe_padic_k{K}")))
     # the K = 37 P-adic kernel with matrix-core Barrett reductions: pseudo-variant 1137; its four-tile body (product 2
     # of the reductions without its fifth M-tile): 1237; the four-tile body on product 1's operand shifted by 8 bytes
-    # (15 instead of 19 product-1 tiles): 1337; with product 1 fed q1's limbs as they lie (no repack): 1437
-    for S, body in ((1137, "m37"), (1237, "m37t"), (1337, "m37s"), (1437, "m37l")):
+    # (15 instead of 19 product-1 tiles): 1337; with product 1 fed q1's limbs as they lie (no repack): 1437; that one
+    # with MUL's cross term by Karatsuba: 1537
+    for S, body in ((1137, "m37"), (1237, "m37t"), (1337, "m37s"), (1437, "m37l"), (1537, "m37k")):
         kernels.append((S, f"fthe_padic_{body}", f"padic_{body}",
-                        lambda body=body: gen_padic_mfma.gen_body(body, m37_ab)))
+                        lambda body=body: gen_padic_mfma.gen_body(body, m37_ab if body != "m37k" else m37k_ab)))
     # the n-adic four-lane kernel of the public-key encrypt (base-n digits of 76 limbs): pseudo-variant 2076
     kernels.append((2076, "fthe_nadic_q76", "nadic_q76", lambda: gen_nadic.gen_nadic(76, 27, "fthe_nadic_q76")))
     # its Montgomery form (LSB-first reductions, no quotient estimates): pseudo-variant 2176

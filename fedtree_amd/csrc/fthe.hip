@@ -44,7 +44,7 @@ using namespace fthe;
 
 namespace {
 
-constexpr int MAX_VARIANTS = 13;
+constexpr int MAX_VARIANTS = 14;
 // s80: four lanes per element mod p^2 / q^2 of Paillier-2048 (small-batch decrypt latency);
 // 1000 + K: the P-adic exponentiation kernels mod P^2 (gen_padic.py, digits of K limbs, slots of 2K
 // limbs; the "S" here only names the variant): K = 37 runs on the s74 slots of Paillier-2048,
@@ -56,21 +56,25 @@ constexpr int MAX_VARIANTS = 13;
 // 1337: fthe_padic_m37s, the four-tile body with product 1's operand shifted by 8 bytes (gen_padic_mfma.py q1_shift:
 // 15 instead of 19 product-1 tiles); its launches are also counted under 1237 and 1137;
 // 1437: fthe_padic_m37l, the four-tile body with product 1 fed q1's radix-2^28 limbs as they lie (gen_padic_mfma.py
-// limb_op: no repack before product 1; a 24 KB tile image, padic_tiles::build_limb), the default for the same P; its
-// launches are also counted under 1337, 1237 and 1137;
+// limb_op: no repack before product 1; a 24 KB tile image, padic_tiles::build_limb); its launches are also counted
+// under 1337, 1237 and 1137;
+// 1537: fthe_padic_m37k, m37l with MUL's cross term x0 y1 + x1 y0 by one level of Karatsuba (gen_padic_mfma.py
+// mul_kara; the same tile image), the default for the same P; its launches are also counted under 1437, 1337, 1237
+// and 1137;
 // 2000 + 76: the n-adic four-lane kernel (gen_nadic.py, base-n digits of 76 limbs) on the s152 slots;
 // 2100 + 76: its Montgomery form (gen_nadic.py mont: LSB-first reductions, no quotient estimates)
 // 2200 + 76: its matrix-core Barrett form (gen_nadicb.py: the products on the VALU, both Barrett reductions by n
 // on i8 MFMA; workgroups of kNbWaves waves, n of 2041..2048 bits)
 constexpr int kPadicS = 1037, kPadicK = 37, kPadicSmallK = 19, kNadicS = 2076, kPadicMfmaS = 1137,
               kNadicMontS = 2176, kNadicBarS = 2276, kPadicMfmaTS = 1237, kPadicMfmaSS = 1337,
-              kPadicMfmaLS = 1437;
+              kPadicMfmaLS = 1437, kPadicMfmaKS = 1537;
 // fthe_padic_m37t: the widest P (TOPEST_MAX_BITS of gen_padic_mfma.py), Pt = P >> kPadicPtShift at ctx word kPadicPtWord
 constexpr int kPadicTopBits = 1027, kPadicPtShift = 1000, kPadicPtWord = 100;
 const Shape kVariants[MAX_VARIANTS] = {{37, 28, 1}, {74, 28, 1}, {152, 27, 4}, {80, 27, 4},
                                        {1000 + kPadicK, 28, 1}, {1000 + kPadicSmallK, 28, 1}, {kNadicS, 27, 4},
                                        {kPadicMfmaS, 28, 1}, {kNadicMontS, 27, 4}, {kNadicBarS, 27, 4},
-                                       {kPadicMfmaTS, 28, 1}, {kPadicMfmaSS, 28, 1}, {kPadicMfmaLS, 28, 1}};
+                                       {kPadicMfmaTS, 28, 1}, {kPadicMfmaSS, 28, 1}, {kPadicMfmaLS, 28, 1},
+                                       {kPadicMfmaKS, 28, 1}};
 constexpr Shape kLatShape{80, 27, 4};
 constexpr int kAddbBlob = 3152;           // fthe_addb_q152's code object in gen/montprog_blobs.h
 
@@ -583,6 +587,7 @@ extern "C" int fthe_ctx_create(int device, fthe_ctx **out) {
         if (kVariants[i].S > 2200) snprintf(name, sizeof name, "fthe_nadic_b%d", kVariants[i].S - 2200);
         else if (kVariants[i].S > 2100) snprintf(name, sizeof name, "fthe_nadic_m%d", kVariants[i].S - 2100);
         else if (kVariants[i].S > 2000) snprintf(name, sizeof name, "fthe_nadic_q%d", kVariants[i].S - 2000);
+        else if (kVariants[i].S > 1500) snprintf(name, sizeof name, "fthe_padic_m%dk", kVariants[i].S - 1500);
         else if (kVariants[i].S > 1400) snprintf(name, sizeof name, "fthe_padic_m%dl", kVariants[i].S - 1400);
         else if (kVariants[i].S > 1300) snprintf(name, sizeof name, "fthe_padic_m%ds", kVariants[i].S - 1300);
         else if (kVariants[i].S > 1200) snprintf(name, sizeof name, "fthe_padic_m%dt", kVariants[i].S - 1200);
@@ -717,17 +722,10 @@ extern "C" int fthe_prof_read(fthe_ctx *c, double *kernel_ms, double *launches, 
             etot += ms; en += 1;
             c->var_ms[c->prof_vi[i]] += ms; c->var_n[c->prof_vi[i]] += 1;
             const int vs = kVariants[c->prof_vi[i]].S;            // the same kernel family: read as 1137 too,
-            if (vs == kPadicMfmaTS || vs == kPadicMfmaSS || vs == kPadicMfmaLS) {   // and the later four-tile
-                const int vm = variant_index(kPadicMfmaS);                         // bodies as their ancestors
-                c->var_ms[vm] += ms; c->var_n[vm] += 1;
-            }
-            if (vs == kPadicMfmaSS || vs == kPadicMfmaLS) {
-                const int vt = variant_index(kPadicMfmaTS);
-                c->var_ms[vt] += ms; c->var_n[vt] += 1;
-            }
-            if (vs == kPadicMfmaLS) {
-                const int vt = variant_index(kPadicMfmaSS);
-                c->var_ms[vt] += ms; c->var_n[vt] += 1;
+            for (const int anc : {kPadicMfmaS, kPadicMfmaTS, kPadicMfmaSS, kPadicMfmaLS}) {   // and the later four-tile
+                if (vs <= anc || vs < kPadicMfmaTS || vs > kPadicMfmaKS) continue;          // bodies as their ancestors
+                const int va = variant_index(anc);
+                c->var_ms[va] += ms; c->var_n[va] += 1;
             }
             eiv.emplace_back(t0, (double)t0 + ms);
         }
@@ -787,6 +785,8 @@ static int padic_digits(const mpz_t P, Shape sh) {
 // operand and image), FTHE_NO_M37T=1 keeps fthe_padic_m37 and so switches off both (bit-identical results).
 // The default for the same P is fthe_padic_m37l (product 1 fed the limbs as they lie; the 24 KB image of
 // padic_tiles::build_limb); FTHE_NO_M37L=1 keeps fthe_padic_m37s, and the older switches switch it off too.
+// Where fthe_padic_m37l is admitted fthe_padic_m37k runs in its place (the same context and image; MUL's cross term
+// by Karatsuba); FTHE_NO_M37K=1 keeps fthe_padic_m37l.
 static int upload_padic(DevMod &d, const mpz_t P, int K) {
     Mpz P2; mpz_mul(P2, P, P);
     d.m.init(P2, Shape{2 * K, 28, 1});
@@ -817,7 +817,8 @@ static int upload_padic(DevMod &d, const mpz_t P, int K) {
     if (hipMalloc(&d.d_ctx, w.size() * 4) != hipSuccess) return FTHE_ERR_NOMEM;
     HIPOK(hipMemcpy(d.d_ctx, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     d.kernel_S = 1000 + K;
-    d.kernel_S_mfma = tiles.empty() ? 0 : limb ? kPadicMfmaLS : shifted ? kPadicMfmaSS : top_ok ? kPadicMfmaTS : kPadicMfmaS;
+    const int limb_S = getenv("FTHE_NO_M37K") ? kPadicMfmaLS : kPadicMfmaKS;
+    d.kernel_S_mfma = tiles.empty() ? 0 : limb ? limb_S : shifted ? kPadicMfmaSS : top_ok ? kPadicMfmaTS : kPadicMfmaS;
     return FTHE_OK;
 }
 // Algorithmic 32-bit MACs of a P-adic program (SURVEY 8(d) units, the executed algorithm): s = words

@@ -40,10 +40,16 @@ and fthe_padic_m37s (top_est=True, q1_shift=8), the same with product 1's operan
 the four tiles with m - k = 1: 15 product-1 tiles, and the image of padic_tiles::build(P, 128, 8).
 A fourth, fthe_padic_m37l (top_est=True, limb_op=True), feeds product 1 the radix-2^28 limbs of q1 as they lie -- no
 repack into base-256 dwords, the tilted band in 15 tiles of their own: the 24 KB image of padic_tiles::build_limb(P).
-BODIES holds the four argument sets and gen_body(variant, ab) generates one by name; the A/B switches (SWITCHES) are
-the argument ab of either, parsed by parse_ab.
+A fifth, fthe_padic_m37k (m37l's arguments with mul_kara=True), forms MUL's cross term x0 y1 + x1 y0 by
+one level of Karatsuba (kara_cross_mul).  Its second parameter fill0 (off in the table, switch fill0) runs the ripples
+of both Karatsuba cross terms and MUL's copy of x0 y0's low half while tile 0 of the first quotient product sits in
+the matrix core: each caller of .Lreduce issues that tile itself, its own fillers between the MFMAs, and enters the
+shared reduction behind it.
+BODIES and K_BODIES hold the five argument sets and gen_body(variant, ab) generates one by name; the A/B switches
+(SWITCHES, and m37k's own K_SWITCHES) are the argument ab of either, parsed by parse_ab.
 """
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -86,15 +92,23 @@ TILE_D2 = (0, 1, 2, 3)          # product-2: k = 0 for m = 0..4 (tiles 10..14), 
 SWITCHES = ("noswap", "nonop", "nomfma", "nodbuf", "nointerleave", "nopair", "noprepair", "nodesync", "noprio",
             "noprexor", "nocmerge", "nokara", "s1lo112", "noq3dw", "clampbr", "noclampbr", "stamp")
 PRIOS = tuple(f"prio{n}" for n in range(4))
+# fthe_padic_m37k's own switches (K_BODIES below; the other bodies do not know them):
+#   nomulkara               MUL's cross term as two plain products (product_cols), not kara_cross_mul
+#   fill0, nofill0          tile 0 of every reduction's first quotient product issued by the caller, the ripples of the
+#                           Karatsuba cross terms (MUL: and the copy of x0 y0's low half) between its MFMAs and in
+#                           place of the three s_nop 7 before its exchange (fill_tile0), or not.  Default: K_BODIES
+#                           (off: no clear gain)
+K_SWITCHES = ("nomulkara", "fill0", "nofill0")
 
 
-def parse_ab(ab):
-    """the switch string (exact tokens between commas) or set -> frozenset of known switches"""
+def parse_ab(ab, more=()):
+    """the switch string (exact tokens between commas) or set -> frozenset of known switches (more: a body's own)"""
     toks = frozenset(t.strip() for t in ab.split(',') if t.strip()) if isinstance(ab, str) else frozenset(ab)
-    unknown = sorted(toks - set(SWITCHES + PRIOS))
+    unknown = sorted(toks - set(SWITCHES + PRIOS + tuple(more)))
     if unknown:
-        raise ValueError(f"unknown m37 switch {', '.join(unknown)}: known are {', '.join(SWITCHES + PRIOS)}")
-    for group in ({"clampbr", "noclampbr"}, {"noprio", *PRIOS}):
+        known = SWITCHES + PRIOS + tuple(more)
+        raise ValueError(f"unknown m37 switch {', '.join(unknown)}: known are {', '.join(known)}")
+    for group in ({"clampbr", "noclampbr"}, {"noprio", *PRIOS}, {"fill0", "nofill0"}):
         if len(toks & group) > 1:
             raise ValueError(f"m37 switches {', '.join(sorted(toks & group))} contradict each other")
     return toks
@@ -102,7 +116,7 @@ def parse_ab(ab):
 
 def s1_lo(ab=""):
     """product 1's first column under the switches ab: the window the tile image must be built for"""
-    return 112 if "s1lo112" in parse_ab(ab) else S1_LO
+    return 112 if "s1lo112" in parse_ab(ab, K_SWITCHES) else S1_LO
 
 
 def tile_index(prod, m, k, q1_shift=0, limb_op=False):
@@ -141,16 +155,22 @@ BODIES = {
     "m37s": dict(top_est=True, q1_shift=Q1_SHIFT, limb_op=False, clampbr=False),
     "m37l": dict(top_est=True, q1_shift=0, limb_op=True, clampbr=True),
 }
+# the fifth body, fthe_padic_m37k: m37l's arguments and two of its own.  It stands beside BODIES and SWITCHES, which
+# name the four bodies that share every switch
+K_BODIES = {"m37k": dict(BODIES["m37l"], mul_kara=True, fill0=False)}
 
 
 def gen_body(variant: str, ab="") -> str:
-    """the kernel fthe_padic_<variant> (a key of BODIES) under the switches ab"""
-    body = {k: v for k, v in BODIES[variant].items() if k != "clampbr"}
+    """the kernel fthe_padic_<variant> (a key of BODIES or K_BODIES) under the switches ab"""
+    body = {k: v for k, v in {**BODIES, **K_BODIES}[variant].items() if k != "clampbr"}
     return gen_padic_mfma("fthe_padic_" + variant, ab=ab, **body)
 
 
-def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op: bool = False, ab="") -> str:
+def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op: bool = False,
+                   mul_kara: bool = False, fill0: bool = False, ab="") -> str:
     """ab: A/B switches (SWITCHES above), a comma-separated string or a set.
+    mul_kara, fill0 (with limb_op: fthe_padic_m37k): MUL's cross term by kara_cross_mul; the first tile of
+    every reduction issued by the caller, its MFMAs spaced with the caller's independent VALU work (fill_tile0).
     limb_op (with top_est: fthe_padic_m37l): product 1 reads its B operands straight from the limbs
     T[36..73] (V[36..73] in the second reduction) behind LIMB_PAD pad dwords -- K index 4 (t + LIMB_PAD) + j is byte j
     of q1's limb t, fed as b ^ 0x80 for j < 3 and as it is for j = 3; the constant digit rides in byte 3 of limb 37
@@ -173,10 +193,10 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     plain residue below 3 P^2 (x1 = its quotient); its own reduction keeps the five-tile product 2."""
     K, B = 37, 28
     MASK = (1 << B) - 1
-    flags = dict(top_est=top_est, q1_shift=q1_shift, limb_op=limb_op)
-    body = [b for b in BODIES.values() if all(b[k] == v for k, v in flags.items())]
+    flags = dict(top_est=top_est, q1_shift=q1_shift, limb_op=limb_op, mul_kara=mul_kara, fill0=fill0)
+    body = [b for b in {**BODIES, **K_BODIES}.values() if all(b.get(k, False) == v for k, v in flags.items())]
     assert body, f"{flags}: not one of BODIES (limb_op and q1_shift = {Q1_SHIFT} need top_est and exclude each other)"
-    ab = parse_ab(ab)
+    ab = parse_ab(ab, K_SWITCHES if mul_kara or fill0 else ())
 
     def refuse(sw, why):
         if sw in ab:
@@ -188,6 +208,9 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         refuse("noprexor", "product 1 reads the limbs as they lie, so they must leave the column tails flipped")
         refuse("noq3dw", "V[36..73] is product 1's operand, so the second q3 has no limbs to land in")
     PREXOR, CMERGE, KARA, Q3DW = (sw not in ab for sw in ("noprexor", "nocmerge", "nokara", "noq3dw"))
+    MULKARA = mul_kara and "nomulkara" not in ab
+    FILL0 = "fill0" in ab or (fill0 and "nofill0" not in ab)
+    assert not (MULKARA and not KARA), "kara_cross_mul keeps its constants where kara_cross does (s76..s78)"
     s1lo = s1_lo(ab)                             # product-1 columns s1lo .. s1lo + 159
     CLAMPBR = "clampbr" in ab or (body[0]["clampbr"] and "noclampbr" not in ab)
     # VALU instructions kept between a tile's last MFMA and the lane exchange that reads its results (>= 24: the
@@ -218,7 +241,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         VV = TT + 2 * K + 2
         V_LDS = VV + 2 * K + 2
         PATV = (V_LDS + 1, V_LDS + 2)
-        NVGPR = V_LDS + 3
+        NVGPR = V_LDS + 3 + MULKARA              # kara_cross_mul takes the last register as a temporary
         assert NVGPR <= 256
     L36 = "v14"                                  # limb_op: the unflipped copy of limb 36 (the remainder's init)
 
@@ -565,6 +588,39 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         rr = (rho & 3) + 4 * (rho >> 3)
         return f"v{(G1x if (rho >> 2) & 1 else G0x) + rr}"
 
+    def fill_tile0(tile, work, nxt):
+        """fill0: tile 0 of the first product 1 (one accumulator set: nothing of the reduction can run beside it) with
+        the caller's independent instructions (work) between its MFMAs -- the wave would issue nothing while the
+        matrix core takes them one after another -- and the last MARGIN of them behind the last MFMA, where three
+        s_nop 7 stood (they stand there still if work is shorter).  What follows is the callers' shared text: the
+        label .Lreduce ends the part each caller issues itself."""
+        issue = capture(lambda: issue_tile(*tile, G0, G1))
+        fill = capture(work)
+        banned = set(range(G0, G0 + 32)) | {int(r[1:]) for r in OPND[0]} | set(range(VA[0], VA[2] + 4)) | {int(L36[1:])}
+        for ins in fill:                         # reordering only: nothing tile 0 or the head before it touches
+            regs = {int(r) for r in re.findall(r'\bv(\d+)\b', ins)}
+            for lo, hi in re.findall(r'\bv\[(\d+):(\d+)\]', ins):
+                regs |= set(range(int(lo), int(hi) + 1))
+            assert ins.lstrip().startswith('v_') and not regs & banned, f"fill0: {ins.strip()} meets tile 0's registers"
+        n_mf = sum('v_mfma' in ins for ins in issue)
+        tail = len(fill) if n_mf == 0 else MARGIN if len(fill) >= MARGIN else 0
+        head = fill[:len(fill) - tail]
+        gaps = max(1, n_mf - 1)
+        seen = 0
+        for ins in issue:
+            e(ins)
+            if 'v_mfma' in ins and seen < gaps:
+                for x in head[seen * len(head) // gaps:(seen + 1) * len(head) // gaps]:
+                    e(x)
+                seen += 1
+        prefetch(*nxt)
+        for x in fill[len(fill) - tail:]:
+            e(x)
+        if tail < MARGIN and "nonop" not in ab:
+            for _ in range(3):
+                e('  s_nop 7')
+        e('.Lreduce:')
+
     def run_tiles(tiles, consume, nxt, dbuf, after_issue0=None):
         """all M-tiles of a product: consume(m, col_reg_of_the_tile) after each; dbuf: two accumulator sets,
         tile m+1's MFMAs issued before tile m's results are folded, so the matrix core works while the
@@ -572,7 +628,11 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         nt = len(tiles)
         if not dbuf:
             for m in range(nt):
-                mtile_mfmas(*tiles[m], nxt=tiles[m + 1] if m < nt - 1 else nxt)
+                if m == 0 and after_issue0 is not None:
+                    fill_tile0(tiles[0], after_issue0, tiles[1])
+                    exchange(G0, G1, waited=True, tile=tuple(tiles[0][:2]))
+                else:
+                    mtile_mfmas(*tiles[m], nxt=tiles[m + 1] if m < nt - 1 else nxt)
                 consume(m, col_reg)
             return
         sets = ((G0, G1), (GB0, GB1))
@@ -734,7 +794,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 
     nclamp = [0]
 
-    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, pre_in=None, dw=None, t4=False):
+    def mfma_barrett(Tl, q3out, clamp, prefetched=False, dbuf=False, pre_in=None, dw=None, t4=False, fill=None):
         """product 1: q3 = Barrett's quotient of T (Tl: 2K limbs, Tl[K-1] < 2^29 allowed) -> q3out (K regs,
         may be Tl[K:]); clamp: q3 = -1 (numerator < 0: q1 = 0, or a small q1 at P near 2^1030) -> 0; prefetched: its first A-tile reads are in flight;
         dbuf: double-buffered accumulators (T[38..69] free); pre_in: Tl[K..2K-1] arrive pre-flipped
@@ -742,7 +802,8 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         dw (no clamp): q3 mod b^K leaves as product 2's operand dwords dw[0..32] instead (byte 0 the constant
         digit 1, the others b ^ 0x80; tools/padic_mfma_model.py fold_dwords); may overlap Tl[K..]
         t4 (top_est): f32 -> V_FRAC for the four-tile product 2, which reads operand dwords 0..31 only: the dword
-        fold ends at dword 31"""
+        fold ends at dword 31
+        fill (fill0, no dbuf): the caller's independent work for tile 0 (fill_tile0)"""
         if pre_in is None:
             pre_in = PREXOR
         if not prefetched:
@@ -794,7 +855,7 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 
         def consume(m, creg):
             fold_columns(ch, tile_cols(1, m, lambda rho: s1lo + 32 * m + rho, creg))
-        run_tiles(P1_TILES, consume, P2_TILES[0], dbuf)
+        run_tiles(P1_TILES, consume, P2_TILES[0], dbuf, after_issue0=fill)
         ch.finish()
         OPND[0] = D
         P1_TOP[0] = S1_TOP
@@ -1017,6 +1078,15 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             terms = [(X0[19 + i], X1[19 + c - i]) for i in range(18) if 0 <= c - i < 18]
             cols.append({'terms': terms, 'dbl': True, 'out': V[38 + c], 'cpl': True, 'last': c == 35})
         columns(cols)
+        return kara_middle(lambda k: [(S0[i], S1[k - i]) for i in range(19) if 0 <= k - i < 19], C)
+
+    RIP = ("v58", "v59") if FILL0 else ("v2", "v3")     # the ripple's value and carry: clear of the A-tile buffers
+
+    def kara_middle(terms_of, C):
+        """steps 3 and 4 of kara_cross / kara_cross_mul: the middle columns (terms_of(k): their multiply-adds) over
+        V[0..18] = P0's low limbs, C = its limbs 19..37 and V[38..73] = P2 complemented; returns the ripple"""
+        TPL = ("v2", "v4")
+        RV, RC = RIP
         e(f'  v_mov_b64_e32 {carry}, 3')
         cols = []
         for k in range(38):                                     # middle columns at b^19
@@ -1031,25 +1101,141 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
             else:                                               # P2_36 = P2_37 = 0: 4 mask - P2c - C
                 pre = [f'  v_sub_u32_e32 {tl}, {S4MASK}, {V[k + 19]}',
                        f'  v_sub_u32_e32 {tl}, {tl}, {C[k - 19]}']
-            terms = [(S0[i], S1[k - i]) for i in range(19) if 0 <= k - i < 19]
-            col = {'terms': terms, 'out': V[k + 19], 'addend': f'v[{tl[1:]}:{int(tl[1:]) + 1}]', 'pre': pre}
+            col = {'terms': terms_of(k), 'out': V[k + 19], 'addend': f'v[{tl[1:]}:{int(tl[1:]) + 1}]', 'pre': pre}
             if PREXOR and k + 19 >= K:
                 col['px'] = pxu(k + 19)
             cols.append(col)
         columns(cols, carry_in=True)
         # 4. ripple: v = (mask ^ P2c_19) + carry - 3, then limb / carry through V[73] (v2 value, v3 carry)
-        e(f'  v_xad_u32 v2, {V[57]}, {SMASK}, v{CARRY}')
-        rip = ['  v_add_u32_e32 v2, -3, v2']
+        e(f'  v_xad_u32 {RV}, {V[57]}, {SMASK}, v{CARRY}')
+        rip = [f'  v_add_u32_e32 {RV}, -3, {RV}']
         for j in range(57, 2 * K):
             px = pxu(j) if PREXOR else None
             if j == 2 * K - 1:
-                rip.append(f'  v_xor_b32_e32 {V[j]}, {px}, v2' if px else f'  v_mov_b32_e32 {V[j]}, v2')
+                rip.append(f'  v_xor_b32_e32 {V[j]}, {px}, {RV}' if px else f'  v_mov_b32_e32 {V[j]}, {RV}')
                 break
-            rip.append(f'  v_bitop3_b32 {V[j]}, v2, {SMASK}, {px} bitop3:0x6a' if px
-                       else f'  v_and_b32_e32 {V[j]}, {hex(MASK)}, v2')
-            rip.append('  v_lshrrev_b32_e32 v3, 28, v2')
-            rip.append(f'  v_xad_u32 v2, {V[j + 1]}, {SMASK}, v3')
+            rip.append(f'  v_bitop3_b32 {V[j]}, {RV}, {SMASK}, {px} bitop3:0x6a' if px
+                       else f'  v_and_b32_e32 {V[j]}, {hex(MASK)}, {RV}')
+            rip.append(f'  v_lshrrev_b32_e32 {RC}, 28, {RV}')
+            rip.append(f'  v_xad_u32 {RV}, {V[j + 1]}, {SMASK}, {RC}')
         return rip
+
+    def kara_cross_mul():
+        """V = W = x0 y1 + x1 y0 (74 limbs, the upper 37 pre-XORed, the constant digit in byte 3 of limb 73) by one
+        level of Karatsuba applied to both products at once -- kara_cross's scheme with P0 = x0L y1L + x1L y0L,
+        P2 = x0H y1H + x1H y0H and the middle (x0L + x0H)(y1L + y1H) + (x1L + x1H)(y0L + y0H), whose sizes are those
+        of 2 x0L x1L, 2 x0H x1H and S0 S1 there, so the addends t', the bias 3 and the ripple are kara_middle's as
+        they stand (bounds: tools/padic_mfma_model.py kara_cross_mul).  Returns (the ripple, the instructions that
+        must follow the middle columns before x0 y0 is formed).
+        Registers.  x0 and y0 outlive W (x0 y0 follows), x1 and y1 die in it, and 15 registers lie idle in a product
+        phase (IDLE below).  P2 comes first, on the raw high halves; then x1H += x1L and y1H += y1L in place
+        (A1, B1; limb 18 of a half sum is the low half's own) while P0 is formed, whose limbs 19..37 (C) go to IDLE
+        and, the last four, to x1's limbs 0..3 (last read 13 columns earlier).  x1L, y1L are then free: they take
+        limbs 2..17 of A0 = x0L + x0H and B0 = y0L + y0H and the addends' zero high dwords stay v3 / v5; limbs 0
+        and 1 of A0 and B0 find no register and are formed in x0H's and y0H's limbs 19, 20, which are restored
+        (minus the low limb) after the middle columns: four more instructions."""
+        assert limb_op and NVGPR == 256
+        IDLE = ["v6", "v7", "v8", "v9", f"v{XA + 37}", f"v{XA + 38}", f"v{XA + 39}", D[37], D[38], D[39],
+                OPB[id(T)][0], OPB[id(T)][39], OPB[id(V)][0], OPB[id(V)][39], "v255"]
+        assert len(set(IDLE)) == 15 and not set(IDLE) & set(X0 + X1 + T + V + [f"v{V_LDS}", *map(pat, (0, 1))])
+        C = IDLE + X1[:4]
+        A1, B1 = X1[19:] + [X1[18]], Y1[19:] + [Y1[18]]
+        pool = X1[4:18] + Y1[:18]
+        A0 = X0[19:21] + pool[:16] + [X0[18]]
+        B0 = Y0[19:21] + pool[16:] + [Y0[18]]
+        assert all(len(x) == 19 for x in (C, A0, A1, B0, B1))
+        cols = []
+        for c in range(36):                                     # P2, complemented
+            terms = []
+            for i in range(18):
+                if 0 <= c - i < 18:
+                    terms += [(X0[19 + i], Y1[19 + c - i]), (X1[19 + i], Y0[19 + c - i])]
+            cols.append({'terms': terms, 'out': V[38 + c], 'cpl': True, 'last': c == 35})
+        columns(cols)
+        bg = []
+        for i in range(18):                                     # the high halves of x1, y1 are spent
+            bg.append(f'  v_add_u32_e32 {A1[i]}, {X1[i]}, {X1[19 + i]}')
+            bg.append(f'  v_add_u32_e32 {B1[i]}, {Y1[i]}, {Y1[19 + i]}')
+        for i in range(2):
+            bg.append(f'  v_add_u32_e32 {A0[i]}, {X0[i]}, {X0[19 + i]}')
+            bg.append(f'  v_add_u32_e32 {B0[i]}, {Y0[i]}, {Y0[19 + i]}')
+        bg += ['  v_mov_b32_e32 v3, 0', '  v_mov_b32_e32 v5, 0']
+        cols = []
+        for c in range(38):                                     # P0
+            terms = []
+            for i in range(19):
+                if 0 <= c - i < 19:
+                    terms += [(X0[i], Y1[c - i]), (X1[i], Y0[c - i])]
+            cols.append({'terms': terms, 'out': V[c] if c < 19 else C[c - 19], 'last': c == 37})
+        columns(cols, bg=bg)
+        for i in range(2, 18):                                  # the low halves of x1, y1 are spent
+            e(f'  v_add_u32_e32 {A0[i]}, {X0[i]}, {X0[19 + i]}')
+            e(f'  v_add_u32_e32 {B0[i]}, {Y0[i]}, {Y0[19 + i]}')
+
+        def mid(k):
+            terms = []
+            for i in range(19):
+                if 0 <= k - i < 19:
+                    terms += [(A0[i], B1[k - i]), (A1[i], B0[k - i])]
+            return terms
+        rip = kara_middle(mid, C)
+        restore = []
+        for i in range(2):
+            restore.append(f'  v_sub_u32_e32 {X0[19 + i]}, {X0[19 + i]}, {X0[i]}')
+            restore.append(f'  v_sub_u32_e32 {Y0[19 + i]}, {Y0[19 + i]}, {Y0[i]}')
+        return rip, restore
+
+    Q = D[2:2 + K]                               # limb_op: the first reduction's q3 limbs
+    RINIT = (lambda Tl: Tl[:K - 1] + [L36]) if limb_op else (lambda Tl: None)
+
+    def reduce_body(fill=None):
+        """the reduction of SQR and MUL, from the label .Lreduce; fill (fill0): the caller's instructions for tile 0
+        of the first product 1 -- the text then starts in the caller and .Lreduce stands behind that tile's issue"""
+        if fill is None:
+            e('.Lreduce:')
+        # default s_setprio 3 over the reduction (noprio: none): -0.5..1% (profiles/r03s_m37_prio_ab.jsonl)
+        PRIO = next((int(t[4:]) for t in ab & set(PRIOS)), 0 if "noprio" in ab else 3)
+        if PRIO:
+            e(f'  s_setprio {PRIO}')                # the latency-bound matrix phases win the SIMD's VALU issue
+        dbuf = "nodbuf" not in ab
+        # the first product 1 has one accumulator set: T[38..69] is its operand (limb_op) or takes its q3, and V is live
+        q3 = mfma_barrett(T, Q if limb_op else T[K:], clamp=True, t4=top_est, fill=fill)    # u1 -> T[K..2K-1]
+
+        def add_u1():
+            for i in range(K):
+                if PREXOR:                                      # V += u1 ^ pat (u1 arrives pre-flipped)
+                    e(f'  v_xad_u32 {V[i]}, {q3[i]}, {pat(i)}, {V[i]}')
+                else:
+                    e(f'  v_add_u32_e32 {V[i]}, {V[i]}, {q3[i]}')  # V += u1 (limbs < 2^29); u1 dies here
+        mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True,
+                       inits=RINIT(T))               # u0 -> T[0..K-1]
+        if Q3DW:
+            mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2, t4=top_est)    # T[K..] is free
+            mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2, t4=top_est, inits=RINIT(V))
+        else:
+            q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf, t4=top_est)
+            mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf, t4=top_est)
+        move(X0, T[:K])
+        move(X1, V[:K])
+        if PRIO:
+            e('  s_setprio 0')
+        e('  s_setpc_b64 s[12:13]')
+
+    REDUCE = []                                  # fill0: the callers' shared text, from .Lreduce on
+
+    def call_reduce(fill):
+        """fill0: the caller issues the reduction up to tile 0 of the first product 1 itself, fill between that tile's
+        MFMAs, and enters the shared text behind it"""
+        if FILL0:
+            nclamp[0] = 1                        # the reduction's clamp label follows LOADP's, as in the other bodies
+            text = capture(lambda: reduce_body(lambda: [e(ins) for ins in fill]))
+            nclamp[0] = 0
+            cut = text.index('.Lreduce:')
+            assert not REDUCE or REDUCE[0] == text[cut:], "the callers of .Lreduce disagree on its text"
+            REDUCE[:] = [text[cut:]]
+            for ins in text[:cut]:
+                e(ins)
+        call('.Lreduce')
 
     # SQR: V = 2 x0 x1, T = x0^2, reduce
     e('.Lsqr:')
@@ -1082,8 +1268,8 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
         elif sq:
             col['terms'] = [(sq, sq)]
         cols.append(col)
-    columns(cols, bg=rip)
-    call('.Lreduce')
+    columns(cols, bg=() if FILL0 else rip)
+    call_reduce(rip)
     e('  s_sub_u32 s19, s19, 1')
     e('  s_branch .Lsqr_loop')
 
@@ -1091,18 +1277,26 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e('.Lmul:')
     Y0, Y1 = T[:K], T[K:]
     load_limbs(Y0 + Y1)
-    columns(product_cols(X0, Y1, 2 * K, V, a2=X1, b2=Y0))
+    rip = []
+    if MULKARA:
+        rip, restore = kara_cross_mul()
+        for ins in restore:
+            e(ins)
+    else:
+        columns(product_cols(X0, Y1, 2 * K, V, a2=X1, b2=Y0))
     TM = X1 + T[K:]                              # x1, y1 dead
-    columns(product_cols(X0, Y0, 2 * K, TM))
-    move(T[:K], X1)
-    call('.Lreduce')
+    columns(product_cols(X0, Y0, 2 * K, TM), bg=() if FILL0 else rip)
+    if FILL0:                                    # limb 36 is read before tile 0 is issued; the rest fills it
+        move(T[K - 1:K], X1[K - 1:])
+        call_reduce(rip + capture(lambda: move(T[:K - 1], X1[:K - 1])))
+    else:
+        move(T[:K], X1)
+        call_reduce(())
     e('  s_branch .Lprog')
 
     # LOADP slot: plain X -> T -> (q3 = x1, r = x0)
     e('.Lloadp:')
     load_limbs(T)
-    Q = D[2:2 + K]                               # limb_op: the first reduction's q3 limbs
-    RINIT = (lambda Tl: Tl[:K - 1] + [L36]) if limb_op else (lambda Tl: None)
     if limb_op:
         q3 = mfma_barrett(T, Q, clamp=True, pre_in=False)
         for i in range(K):                       # x1 waits, unflipped, where product 1's operand has died
@@ -1159,34 +1353,11 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
     e('  s_endpgm')
 
     # reduce (SQR, MUL): T (x0^2 or x0 y0), V (cross terms) -> x0 = T mod P, x1 = (V + T div P) mod P
-    e('.Lreduce:')
-    # default s_setprio 3 over the reduction (noprio: none): -0.5..1% (profiles/r03s_m37_prio_ab.jsonl)
-    PRIO = next((int(t[4:]) for t in ab & set(PRIOS)), 0 if "noprio" in ab else 3)
-    if PRIO:
-        e(f'  s_setprio {PRIO}')                # the latency-bound matrix phases win the SIMD's VALU issue
-    dbuf = "nodbuf" not in ab
-    # the first product 1 has one accumulator set: T[38..69] is its operand (limb_op) or takes its q3, and V is live
-    q3 = mfma_barrett(T, Q if limb_op else T[K:], clamp=True, t4=top_est)    # u1 -> T[K..2K-1]
-
-    def add_u1():
-        for i in range(K):
-            if PREXOR:                                      # V += u1 ^ pat (u1 arrives pre-flipped)
-                e(f'  v_xad_u32 {V[i]}, {q3[i]}, {pat(i)}, {V[i]}')
-            else:
-                e(f'  v_add_u32_e32 {V[i]}, {V[i]}, {q3[i]}')  # V += u1 (limbs < 2^29); u1 dies here
-    mfma_remainder(T, q3, T[:K], nxt_p1=True, dbuf=dbuf, after_pack=add_u1, t4=top_est, clamped=True,
-                   inits=RINIT(T))               # u0 -> T[0..K-1]
-    if Q3DW:
-        mfma_barrett(V, None, clamp=False, prefetched=True, dbuf=dbuf, dw=D2, t4=top_est)    # T[K..] is free
-        mfma_remainder(V, None, V[:K], nxt_p1=False, dbuf=dbuf, dw=D2, t4=top_est, inits=RINIT(V))
+    if FILL0:
+        for ins in REDUCE[0]:
+            e(ins)
     else:
-        q3b = mfma_barrett(V, V[K:], clamp=False, prefetched=True, dbuf=dbuf, t4=top_est)
-        mfma_remainder(V, q3b, V[:K], nxt_p1=False, dbuf=dbuf, t4=top_est)
-    move(X0, T[:K])
-    move(X1, V[:K])
-    if PRIO:
-        e('  s_setprio 0')
-    e('  s_setpc_b64 s[12:13]')
+        reduce_body()
 
     e(f'.Lfunc_end_{name}:')
     e(f'  .size {name}, .Lfunc_end_{name}-{name}')
@@ -1198,8 +1369,8 @@ def gen_padic_mfma(name: str, top_est: bool = False, q1_shift: int = 0, limb_op:
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser()
-    ap.add_argument('--body', default='m37', choices=sorted(BODIES), help='the kernel fthe_padic_<body>')
-    ap.add_argument('--ab', default='', help='A/B switches, comma-separated: ' + ', '.join(SWITCHES) + ', prioN')
+    ap.add_argument('--body', default='m37', choices=sorted({**BODIES, **K_BODIES}), help='the kernel fthe_padic_<body>')
+    ap.add_argument('--ab', default='', help='A/B switches, comma-separated: ' + ', '.join(SWITCHES + K_SWITCHES) + ', prioN')
     ap.add_argument('-o', '--out', required=True)
     a = ap.parse_args()
     with open(a.out, 'w') as f:

@@ -573,7 +573,7 @@ int fthe_debug_nadicb_image(const uint32_t *n, int n_words, uint8_t *out, size_t
 int fthe_debug_nadicb_prog(fthe_key *key, fthe_ctx *ctx, const uint32_t *prog, int prog_words, const uint32_t *in,
                            int nslots, size_t count, int out_slot, uint32_t *out);
 /* The same hook for the key holder's K = 37 P-adic kernel (y^P and c^(P-1) mod P^2 of a Paillier-2048 key): side 0 / 1
- * selects the p / q context, and the body the key chose at set-up runs (fthe_padic_m37l, m37s, m37t, m37, or
+ * selects the p / q context, and the body the key chose at set-up runs (fthe_padic_m37k, m37l, m37s, m37t, m37, or
  * fthe_padic_k37 under FTHE_NO_PADIC_MFMA).  Slots are nslots x count x 74 limbs of 28 bits: a digit pair (x0 in limbs
  * 0..36, x1 in 37..73), or for LOADP / STOREP a plain value in all 74.  FTHE_ERR_NOPRIV on a public key,
  * FTHE_ERR_UNSUPPORTED unless the key runs the K = 37 kernel on its CRT slots (P of 1009..1030 bits).

@@ -1,7 +1,7 @@
 """Crafted digits for the two matrix-core Barrett kernel families, one list for every level that tests them, and the
 checker of what a kernel returns.
 
-The key holder's P-adic kernels (fthe_padic_m37 / m37t / m37s / m37l and the VALU fthe_padic_k37: X mod P^2 as two
+The key holder's P-adic kernels (fthe_padic_m37 / m37t / m37s / m37l / m37k and the VALU fthe_padic_k37: X mod P^2 as two
 base-P digits of 37 limbs of 28 bits) and the parties' fthe_nadic_b76 (X mod n^2 as two base-n digits of 76 limbs of
 27 bits) reduce every product with Barrett's quotient estimate and never correct the remainder: a digit may stay as
 large as `top` = 5P - 1 (m37, k37), 3P - 1 (the four-tile bodies), 3n - 1 (b76), and the next product must take it.
@@ -54,11 +54,15 @@ NADICB_PROGS = {
 PK, PB = 37, 28
 PMASK = (1 << PB) - 1
 BODIES = ("m37l", "m37s", "m37t", "m37", "k37")
-FOUR_TILE = ("m37l", "m37s", "m37t")
+# fthe_padic_m37k (m37l with MUL's cross term by Karatsuba) stands beside BODIES: the same contract, model and image
+# as m37l, its own product cases (padic_kara_mul_pairs)
+LIMB_FED = ("m37k", "m37l")
+FOUR_TILE = LIMB_FED + ("m37s", "m37t")
 # the environment that makes key set-up choose a body, and the profiling variant id that then counts its launches
-BODY_ENV = {"m37l": {}, "m37s": {"FTHE_NO_M37L": "1"}, "m37t": {"FTHE_NO_M37S": "1"}, "m37": {"FTHE_NO_M37T": "1"},
+BODY_ENV = {"m37k": {}, "m37l": {"FTHE_NO_M37K": "1"}, "m37s": {"FTHE_NO_M37L": "1"}, "m37t": {"FTHE_NO_M37S": "1"},
+            "m37": {"FTHE_NO_M37T": "1"},
             "k37": {"FTHE_NO_PADIC_MFMA": "1"}}
-BODY_ID = {"k37": 1037, "m37": 1137, "m37t": 1237, "m37s": 1337, "m37l": 1437}
+BODY_ID = {"k37": 1037, "m37": 1137, "m37t": 1237, "m37s": 1337, "m37l": 1437, "m37k": 1537}
 
 
 def padic_body_for(P, variant):
@@ -147,6 +151,25 @@ def padic_mul_pairs(P, variant):
     return out
 
 
+def padic_kara_mul_pairs(P, variant):
+    """operands ((a0, a1), (b0, b1)) at the extremes of the Karatsuba cross term a0 b1 + a1 b0 of fthe_padic_m37k:
+    every low half all ones under zero high halves and the reverse (the largest P0 / P2 against the smallest middle
+    term and the other way round: the two ends of the middle columns' addend), every limb 2^28 - 1 up to the digit
+    bound (the largest middle column), zero digits and zero cross terms (the carry's bias must ripple out through
+    limbs 57..73), a0 b0 < P (a zero first quotient); then padic_mul_pairs"""
+    sp = padic_special_digits(P, variant)
+    big, low19, high18 = sp[0], sp[3], sp[4]
+    top = padic_nd(variant) * P - 1
+    out = [((low19, low19), (low19, low19)), ((high18, high18), (high18, high18)),
+           ((low19, high18), (low19, high18)), ((low19, high18), (high18, low19)), ((high18, low19), (low19, high18)),
+           ((big, big), (big, big)), ((top, top), (top, top)), ((big, top), (top, big)),
+           ((0, 0), (0, 0)), ((big, 0), (big, 0)), ((top, 0), (top, 0)), ((0, 0), (top, top)), ((top, top), (0, 0)),
+           ((1, big), (1, big)), ((1 << 504, low19), ((P - 1) >> 504, high18))]
+    for (a0, _), (b0, _) in out[-2:]:
+        assert a0 * b0 < P
+    return out + padic_mul_pairs(P, variant)
+
+
 def padic_plain_values(P, variant):
     """LOADP inputs: the values of wave_emu.m37_selftest (0, 1, P - 1, P, P^2 - 1), the neighbours of P^2, values around
     b^36 (below it the quotient is clamped) and the largest admitted X"""
@@ -178,7 +201,7 @@ def _padic_barrett(P, variant):
     if variant == "k37":
         key, red = pm.PadicKey(P, PK), mm.pm_barrett
     else:
-        key = mm.MfmaKey(P, q_shift=mm.Q1_SHIFT if variant == "m37s" else 0, limb_op=variant == "m37l")
+        key = mm.MfmaKey(P, q_shift=mm.Q1_SHIFT if variant == "m37s" else 0, limb_op=variant in LIMB_FED)
         if variant in FOUR_TILE:
             red = lambda k, T: mm.barrett_top(k, T)[:2]            # noqa: E731
         else:

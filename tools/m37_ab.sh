@@ -8,6 +8,8 @@
 #   bash tools/m37_ab.sh TAG t s
 # A variant named l or l_* holds fthe_padic_m37l (--body m37l) and reads the limb-fed tile image:
 #   bash tools/m37_ab.sh TAG s l
+# A variant named k or k_* holds fthe_padic_m37k (--body m37k) and reads the same image:
+#   bash tools/m37_ab.sh TAG l k k_nomulkara k_fill0
 T=${1:?tag}; shift
 N=${M37_LANES:-393216}
 mkdir -p gpurun_out
@@ -21,6 +23,7 @@ for r in 1 2 3; do
     unset M37_KERNEL; [[ $v == t || $v == t_* ]] && export M37_KERNEL=fthe_padic_m37t
     export M37_QSHIFT=0; [[ $v == s || $v == s_* ]] && export M37_KERNEL=fthe_padic_m37s M37_QSHIFT=8
     export M37_LIMB=0; [[ $v == l || $v == l_* ]] && export M37_KERNEL=fthe_padic_m37l M37_LIMB=1
+    [[ $v == k || $v == k_* ]] && export M37_KERNEL=fthe_padic_m37k M37_LIMB=1
     M37_BLOCK=$blk timeout -k 10 120 tools/bin/test_padic tools/bin/m37_$v.hsaco $N 0 fthe_padic_m37 > gpurun_out/${T}_one.json
     rc=$?
     # timing-only variants (nomfma, noswap, nonop: wrong results by design) may report bad lanes (rc 1)

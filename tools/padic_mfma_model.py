@@ -542,6 +542,72 @@ def barrett(key, T, clamp=True):
     return q3, r, clamped
 
 
+KARA_H = 19                      # kara_cross / kara_cross_mul: a digit's low half is limbs 0..18, its high half 19..36
+
+
+def kara_cross_mul(x0, x1, y0, y1):
+    """MUL's cross term W = x0 y1 + x1 y0 as fthe_padic_m37k forms it (gen_padic_mfma.py kara_cross_mul),
+    instruction for instruction on one lane's limbs: P2 and P0 by product scanning, the half sums, the middle columns
+    with the biased addend t' and the carry from 3, the ripple through limbs 57..73.  Asserts every bound the kernel
+    relies on -- limbs below 2^28 and P2's top limb too (stored by XOR), half sums below 2^29, a middle column within
+    38 2^58 + t' + carry < 2^64, t' in [0, 2^30) ([0, 2^31) in column 18), the ripple's 32-bit values non-negative,
+    W < 2^LIMB_T_BITS (byte 3 of limb 73 carries the constant digit) -- and that the 74 limbs returned hold
+    x0 y1 + x1 y0."""
+    H = KARA_H
+    for d in (x0, x1, y0, y1):
+        assert len(d) == K and all(0 <= v <= MASK for v in d)
+
+    def scan(pairs, n):
+        """limbs 0..n-1 of sum a b over (a, b) in pairs by product scanning: 64-bit columns, 28-bit limbs, the last
+        limb unmasked"""
+        out, carry = [], 0
+        for c in range(n):
+            col = carry
+            for a, b in pairs:
+                col += sum(a[i] * b[c - i] for i in range(len(a)) if 0 <= c - i < len(b))
+            assert 0 <= col < (1 << 64)
+            out.append(col & MASK if c < n - 1 else col)
+            carry = col >> B
+        return out
+    lo, hi = (lambda d: d[:H]), (lambda d: d[H:])
+    P2 = scan([(hi(x0), hi(y1)), (hi(x1), hi(y0))], 2 * (K - H))
+    assert P2[-1] <= MASK, "P2's top limb is complemented by XOR with the mask"
+    P2c = [MASK - v for v in P2]                                 # V[38..73]
+    P0 = scan([(lo(x0), lo(y1)), (lo(x1), lo(y0))], 2 * H)
+    assert P0[-1] < (1 << 29)
+    Vl, C = P0[:H], P0[H:]                                       # V[0..18], C (limb 37 unmasked)
+    half = lambda d: [d[i] + d[H + i] for i in range(K - H)] + [d[H - 1]]      # noqa: E731
+    A0, A1, B0, B1 = half(x0), half(x1), half(y0), half(y1)
+    assert all(v < (1 << 29) for s in (A0, A1, B0, B1) for v in s), "half sum limb"
+    mid, carry = [], 3
+    for k in range(2 * H):
+        if k < H:
+            t = C[k] - Vl[k] + P2c[k] + 2 * MASK
+        elif k < 2 * (K - H):
+            t = P2c[k] - P2c[k - H] - C[k - H] + 3 * MASK
+        else:
+            t = 4 * MASK - P2c[k - H] - C[k - H]
+        # column 18 takes P0's limb 37, which is not masked (below 2^29): t' < 2^29 + 3 mask there, still a dword
+        assert 0 <= t < ((1 << 31) if k == H - 1 else (1 << 30)), ("t'", k, t)
+        prod = sum(A0[i] * B1[k - i] + A1[i] * B0[k - i] for i in range(H) if 0 <= k - i < H)
+        assert prod <= 38 << 58
+        col = prod + t + carry
+        assert col < (1 << 64)
+        mid.append(col & MASK)
+        carry = col >> B
+    W = Vl + mid + P2c[H:]                                       # limbs 0..18, 19..56, 57..73 (complemented)
+    v = (W[57] ^ MASK) + carry - 3                               # 32-bit lane arithmetic
+    assert 0 <= carry - 3 and 0 <= v < (1 << 32)
+    for j in range(57, 2 * K - 1):
+        W[j] = v & MASK
+        v = (W[j + 1] ^ MASK) + (v >> B)
+        assert 0 <= v < (1 << 32)
+    W[2 * K - 1] = v
+    assert v < (1 << (LIMB_T_BITS - B * (2 * K - 1))), "W reaches byte 3 of limb 73"
+    assert pm.value(W) == pm.value(x0) * pm.value(y1) + pm.value(x1) * pm.value(y0) and max(W) <= MASK
+    return W
+
+
 pm_barrett = pm.barrett
 
 

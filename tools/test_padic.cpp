@@ -6,6 +6,7 @@
 //        fthe_padic_m37t (its four-tile body: ctx also carries Pt = P >> 1000 at word 100)
 //        fthe_padic_m37s (the four-tile body on the shifted operand: M37_QSHIFT=8 selects its tile image)
 //        fthe_padic_m37l (the four-tile body on the limb-fed operand: M37_LIMB=1 selects its 24 KB tile image)
+//        fthe_padic_m37k (m37l with MUL's cross term by Karatsuba: the same image, M37_LIMB=1)
 // Checks sampled lanes against GMP's mpz_powm and prints the launch time and products per second.
 #include <hip/hip_runtime.h>
 #include <gmp.h>

@@ -9,7 +9,7 @@ workgroup is emulated wave by wave: every wave up to its s_barrier, then each wa
 waves share only what they wrote before the barrier).
 
   python tools/wave_emu.py         (self-test: 16 random adds mod n^2 and edge cases vs Python integers)
-  python tools/wave_emu.py m37     (m37t, m37s, m37l: the other bodies; one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
+  python tools/wave_emu.py m37     (m37t, m37s, m37l, m37k: the other bodies; one wave of fthe_padic_m37: LOADP, STOREX, SQR, MUL, STOREP = x^3 mod P^2)
 """
 import os
 import random
@@ -811,9 +811,13 @@ def _cases():
     return barrett_cases
 
 
+LIMB_FED = ('m37l', 'm37k')                      # the bodies on the 24 KB image of the limb-fed product 1
+
+
 def _m37_asm(variant, ab):
     """the kernel text of a variant (gen_padic_mfma.BODIES: 'm37', 'm37t', the four-tile product 2, 'm37s', m37t with
-    product 1's operand shifted by 8 bytes, or 'm37l', m37t with product 1 fed the limbs as they lie) under the
+    product 1's operand shifted by 8 bytes, 'm37l', m37t with product 1 fed the limbs as they lie, or K_BODIES' 'm37k',
+    m37l with MUL's cross term by Karatsuba) under the
     generator switches ab, the generator, and product 1's first column (s1lo112 needs the matching image)"""
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, os.path.join(here, '..', 'fedtree_amd', 'csrc'))
@@ -825,7 +829,7 @@ def _m37_asm(variant, ab):
 def _m37_ctx(gm, mm, P, s1_lo, variant):
     """the key context: -P limbs, Pt = P >> 1000 (m37t, m37s), the tile image (m37s: the shifted layout)"""
     K, B = 37, 28
-    ctx = bytearray(gm.TILE_OFF + (gm.TILE_BYTES_L if variant == 'm37l' else gm.TILE_BYTES))
+    ctx = bytearray(gm.TILE_OFF + (gm.TILE_BYTES_L if variant in LIMB_FED else gm.TILE_BYTES))
     for j in range(K):                                           # -P limbs (int32)
         ctx[4 * j:4 * j + 4] = ((-((P >> (B * j)) & ((1 << B) - 1))) & M32).to_bytes(4, 'little')
     if variant != 'm37':
@@ -833,7 +837,7 @@ def _m37_ctx(gm, mm, P, s1_lo, variant):
         ctx[gm.PT_OFF:gm.PT_OFF + 4] = (P >> gm.PT_SHIFT).to_bytes(4, 'little')
     assert gm.Q1_SHIFT == mm.Q1_SHIFT
     img = mm.MfmaKey(P, s1_lo=s1_lo, q_shift=mm.Q1_SHIFT if variant == 'm37s' else 0,
-                     limb_op=variant == 'm37l').tile_image()
+                     limb_op=variant in LIMB_FED).tile_image()
     ctx[gm.TILE_OFF:gm.TILE_OFF + len(img)] = img
     return ctx
 
@@ -873,8 +877,8 @@ def m37_selftest(seed=1, ab=None, bits=1024, extra=(), variant='m37', P=None, ju
         (L * 4).to_bytes(4, 'little') + (S * L * 4).to_bytes(4, 'little') + L.to_bytes(4, 'little') + \
         (1).to_bytes(4, 'little') + bytes(128)
     mem.alloc(karg, KA)
-    # m37l: the pad registers beside T[36..73] and V[36..73]
-    pads = (136, 175, 212, 251) if variant == 'm37l' else (60, 61, 97, 98, 99)
+    # m37l, m37k: the pad registers beside T[36..73] and V[36..73]
+    pads = (136, 175, 212, 251) if variant in LIMB_FED else (60, 61, 97, 98, 99)
     junk = {r: [rng.getrandbits(32) for _ in range(64)] for r in pads} if junk_pads else None
     steps = run_workgroup(asm, lds_bytes, 4, mem, KA, 0, nv, finish=(0,), junk=junk)
     bad = 0
@@ -946,10 +950,76 @@ def m37_digits_selftest(seed=1, ab=None, bits=1030, variant='m37', P=None, pairs
     return bad
 
 
+def m37_prog_selftest(prog, slots, out_slot, variant='m37k', P=None, ab=None, junk=None):
+    """wave 0 of a P-adic matrix-core body on a program of its own: slots = {slot: 64 rows of 74 limbs} (the inputs),
+    prog the flat (op, argument) list as the kernel reads it; returns the 64 rows of out_slot as the kernel left
+    them.  junk: {VGPR: 64 start values} (registers the kernel must not rely on)."""
+    asm, gm, s1_lo = _m37_asm(variant, ab)
+    import padic_mfma_model as mm
+    S, L = 74, 256
+    nv = int(re.search(r'\.amdhsa_next_free_vgpr (\d+)', asm).group(1))
+    lds_bytes = int(re.search(r'\.amdhsa_group_segment_fixed_size (\d+)', asm).group(1))
+    ctx = _m37_ctx(gm, mm, P, s1_lo, variant)
+    ns = max(list(slots) + [out_slot]) + 1
+    buf = bytearray(ns * S * L * 4)
+    for s_, rows in slots.items():
+        assert len(rows) == 64
+        for g_, row in enumerate(rows):
+            for k, v in enumerate(row):
+                off = (s_ * S + k) * L * 4 + 4 * g_
+                buf[off:off + 4] = int(v).to_bytes(4, 'little')
+    mem = Mem()
+    SB, PB, CB, KA = 0x10000000, 0x20000000, 0x30000000, 0x40000000
+    mem.alloc(buf, SB)
+    mem.alloc(b''.join(w.to_bytes(4, 'little') for w in prog), PB)
+    mem.alloc(bytes(ctx), CB)
+    karg = SB.to_bytes(8, 'little') + PB.to_bytes(8, 'little') + CB.to_bytes(8, 'little') + \
+        (L * 4).to_bytes(4, 'little') + (S * L * 4).to_bytes(4, 'little') + L.to_bytes(4, 'little') + \
+        (1).to_bytes(4, 'little') + bytes(128)
+    mem.alloc(karg, KA)
+    run_workgroup(asm, lds_bytes, 4, mem, KA, 0, nv, finish=(0,), junk=junk)
+    return [[mem.read(SB + (out_slot * S + k) * L * 4 + 4 * g_, 4) for k in range(S)] for g_ in range(64)]
+
+
+def m37_mul_selftest(seed=1, ab=None, variant='m37k', P=None, bits=1024, operands=None):
+    """wave 0 on single products (LOADX a; MUL b; STOREX): operands ((a0, a1), (b0, b1)) -- default
+    barrett_cases.padic_kara_mul_pairs, the extremes of fthe_padic_m37k's Karatsuba cross term and the products every
+    body is run on -- take the first lanes, random digits below 3P the rest.  Every lane: the model's bounds on the
+    cross term (padic_mfma_model.kara_cross_mul), and what the kernel stored: limbs below 2^28, digits below
+    P + 2^1015 (what the four-tile bodies promise of a product; at P just above 2^1008 two operands at the digit
+    bound 3P - 1 leave x1 = 3P, in fthe_padic_m37l alike, so barrett_cases.check_padic's 3P is not asked here), the
+    residue exact."""
+    import padic_mfma_model as mm
+    bc = _cases()
+    rng = random.Random(seed)
+    if P is None:
+        P = rng.getrandbits(bits) | (1 << (bits - 1)) | (1 << (bits - 2)) | 1
+    ops = list(bc.padic_kara_mul_pairs(P, variant) if operands is None else operands)
+    assert len(ops) <= 64
+    nd = bc.padic_nd(variant)
+    while len(ops) < 64:
+        ops.append((bc.filler(rng, nd * P), bc.filler(rng, nd * P)))
+    prog = bc.PADIC_PROGS["mul"][:4] + [bc.STOREX, 2, 0, 0]
+    out = m37_prog_selftest(prog, {0: [bc.padic_row(a) for a, _ in ops], 1: [bc.padic_row(b) for _, b in ops]}, 2,
+                            variant=variant, P=P, ab=ab)
+    bad = 0
+    for g_, (a, b) in enumerate(ops):
+        mm.kara_cross_mul(*(bc.plimbs(d) for d in (a[0], a[1], b[0], b[1])))
+        val = lambda ls: sum(v << (28 * i) for i, v in enumerate(ls))      # noqa: E731
+        x0, x1 = val(out[g_][:37]), val(out[g_][37:])
+        if not (max(out[g_]) < (1 << 28) and max(x0, x1) < P + (1 << 1015) and
+                (x0 + x1 * P) % (P * P) == (a[0] + a[1] * P) * (b[0] + b[1] * P) % (P * P)):
+            bad += 1
+            if bad <= 3:
+                print(f"  lane {g_}: x0 {x0:#x} x1 {x1:#x}: a {a[0]:#x} {a[1]:#x} b {b[0]:#x} {b[1]:#x}")
+    print(f"{variant} products ({ab or 'default'}): 64 lanes, {bad} mismatches")
+    return bad
+
+
 if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'nadicb':
         sys.exit(1 if nadicb_selftest(waves=int(sys.argv[2]) if len(sys.argv) > 2 else 1) else 0)
-    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s', 'm37l'):
+    if len(sys.argv) > 1 and sys.argv[1] in ('m37', 'm37t', 'm37s', 'm37l', 'm37k'):
         sys.exit(1 if m37_selftest(ab=sys.argv[2] if len(sys.argv) > 2 else None, variant=sys.argv[1]) else 0)
     if len(sys.argv) > 1 and sys.argv[1] == 'addb':          # addb nokara,slowall: a switch string of gen_addb
         selftest(dbg=",".join(sys.argv[2:]))
