@@ -124,7 +124,7 @@ def build_lib():
     srcs = [os.path.join(CSRC, "fthe.hip"), os.path.join(CSRC, "fthe_glue.hip"), os.path.join(CSRC, "fthe_hist.hip"),
             os.path.join(CSRC, "fthe_dec.hip"), os.path.join(CSRC, "fthe_wire.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("bn_host.hpp", "fthe_glue.h", "padic_tiles.hpp", "barrett_image.hpp",
-                                                    "addb_image.hpp", "nadicb_image.hpp")] + \
+                                                    "addb_image.hpp", "nadicb_image.hpp", "group_commit.hpp")] + \
         [os.path.join(GEN, "montprog_blobs.h"), os.path.join(GEN, "addb_layout.h"), os.path.join(GEN, "nadicb_layout.h"),
          os.path.join(HERE, "..", "include", "fthe.h")]
     cmd = ["/opt/rocm/bin/hipcc", f"--offload-arch={ARCH}", "-O3", "-fPIC", "-shared", "-std=c++17",

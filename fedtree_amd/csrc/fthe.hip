@@ -32,6 +32,7 @@
 
 #include "../../include/fthe.h"
 #include "bn_host.hpp"
+#include "group_commit.hpp"
 #include "padic_tiles.hpp"
 #include "addb_image.hpp"
 #include "nadicb_image.hpp"
@@ -326,7 +327,7 @@ struct DevMod {
     }
 };
 
-// Group-commit queue of fthe_decrypt_shared (one per key, created on first use).
+// Group-commit queues of the shared calls (group_commit.hpp; one set per key, created on first use).
 struct DecReq {
     const uint32_t *ct; size_t count; uint64_t *m_low; uint32_t *m_full; bool short_pt;
     int rc = FTHE_OK; bool done = false;
@@ -339,26 +340,38 @@ struct OpReq {                               // fthe_add_shared / fthe_scalar_mu
     bool mul; const uint32_t *a, *b; uint64_t k; size_t count; uint32_t *out;
     int rc = FTHE_OK; bool done = false;
 };
+// Staging buffers of the shared queues above this many bytes are released after their batch
+// (one large shared call must not pin a second copy of its ciphertexts for the key's lifetime).
+constexpr size_t kCoalesceKeepBytes = (size_t)64 << 20;
+template <class V> static void trim(V &v) {
+    if (v.capacity() * sizeof(typename V::value_type) > kCoalesceKeepBytes) { V().swap(v); }
+}
+// A queue and the key's own context its leaders run on (created by the first one).
+template <class Req>
+struct SharedQueue : GroupCommit<Req> {
+    fthe_ctx *ctx = nullptr;
+    int context(int device) { return ctx ? FTHE_OK : fthe_ctx_create(device, &ctx); }
+    ~SharedQueue() { if (ctx) fthe_ctx_destroy(ctx); }
+};
+// The three queues share no state: each has its own lock, leader, context and staging vectors.
 struct Coalescer {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<DecReq *> pending;
-    std::vector<EncReq *> epending;          // fthe_encrypt_shared: its own leader and context
-    std::vector<OpReq *> opending;           // fthe_add_shared / _scalar_mul_u64_shared: a third one
-    bool leader = false, eleader = false, oleader = false;
-    fthe_ctx *ctx = nullptr, *ectx = nullptr, *octx = nullptr;   // the key's own contexts, one leader each
-    // group-commit linger (linger() below): requests in each queue's previous batch, a leader waiting
-    std::condition_variable lcv;
-    size_t last = 0, elast = 0, olast = 0;
-    int64_t last_us = 0, elast_us = 0, olast_us = 0;   // the previous batch's duration
-    bool lingering = false, elingering = false, olingering = false;
-    std::vector<uint32_t> ct, full, eout, oa, ob, oout;
-    std::vector<uint64_t> lo, em;
-    ~Coalescer() {
-        if (ctx) fthe_ctx_destroy(ctx);
-        if (ectx) fthe_ctx_destroy(ectx);
-        if (octx) fthe_ctx_destroy(octx);
-    }
+    struct Dec : SharedQueue<DecReq> {
+        std::vector<uint32_t> ct, full; std::vector<uint64_t> lo;
+        void trim_staging() { trim(ct); trim(lo); trim(full); }
+    } dec;
+    struct Enc : SharedQueue<EncReq> {
+        std::vector<uint64_t> m; std::vector<uint32_t> out;
+        void trim_staging() { trim(m); trim(out); }
+    } enc;
+    struct Ops : SharedQueue<OpReq> {
+        std::vector<uint32_t> a, b, out;
+        void trim_staging() { trim(a); trim(b); trim(out); }
+    } ops;
+};
+// A runner's staging vectors are trimmed after its batch, also when the batch throws.
+template <class Q> struct TrimAfter {
+    Q &q;
+    ~TrimAfter() { q.trim_staging(); }
 };
 
 // A named constant (S limbs) on the device.
@@ -4339,14 +4352,30 @@ struct HostIO {
 };
 }  // namespace
 
+// One input in, one output out (io[0] -> io[2]) around a device-resident call.
+template <class Call>
+static int host_in_out(fthe_ctx *c, const void *in, size_t in_bytes, void *out, size_t out_bytes, Call &&call) {
+    HIPOK(hipSetDevice(c->device));
+    HostIO io{c}; void *din, *dout; int rc;
+    if ((rc = io.in(0, in, in_bytes, &din))) return rc;
+    if ((rc = io.outbuf(2, out_bytes, &dout))) return rc;
+    if ((rc = call((const uint32_t *)din, (uint32_t *)dout))) return rc;
+    return io.back(out, dout, out_bytes);
+}
+
+// Words of injected randomness per ciphertext a host-resident encrypt accepts for these flags (r == nullptr: none).
+static bool r_words_ok(const fthe_key *k, const uint32_t *r, int r_words, int flags) {
+    return !r || (r_words > 0 && r_words <= ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
+                                             : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)));
+}
+
 // Host-resident encrypt: inputs staged and outputs drained chunk by chunk through pinned buffers
 // (HostPipe); m is either u64 codec values or general plaintexts of mww words.
 static int encrypt_host(fthe_key *k, fthe_ctx *c, const void *m, int mww, size_t count, const uint32_t *r,
                         int r_words, uint64_t rng_seed, uint32_t *out, int flags, uint64_t index0 = 0) {
     if (!k || !c || (!m && count) || (!out && count)) return FTHE_ERR_ARG;
     if (mww && (mww < 0 || mww > k->n_words)) return FTHE_ERR_ARG;
-    if (r && (r_words <= 0 || r_words > ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
-                                         : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)))) return FTHE_ERR_ARG;
+    if (!r_words_ok(k, r, r_words, flags)) return FTHE_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     size_t cw = 2 * (size_t)k->n_words, mb = mww ? (size_t)mww * 4 : 8;
     int rc;
@@ -4403,71 +4432,15 @@ extern "C" int fthe_decrypt(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t
     return decrypt_host(k, c, ct, count, m_low, m_full, false);
 }
 
-// Host-resident packed pairs.  The floats and codes are 8 to 24 bytes per pair beside 8 n_words of
-// ciphertext: they cross in one copy each, and only the ciphertext rows (and injected r) go through the pipe.
-extern "C" int fthe_encrypt_gh_packed(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
-                                      const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
-                                      uint32_t *out, int flags) {
-    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
-    if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
-    if (r && (r_words <= 0 || r_words > ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
-                                         : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)))) return FTHE_ERR_ARG;
+// Host-resident packed and slot-packed pairs.  The floats and codes are 8 to 24 bytes per pair beside 8 n_words of
+// ciphertext per row: they cross in one copy each, and only the rows ciphertexts (and injected r, one per row) go
+// through the pipe.  impl(g, h, r, out, pipe) is the encrypt on the staged device pointers.
+template <class Impl>
+static int encrypt_gh_host(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count, size_t rows,
+                           const uint32_t *r, int r_words, uint32_t *out, Impl &&impl) {
     HIPOK(hipSetDevice(c->device));
     const size_t cw = 2 * (size_t)k->n_words;
     int rc;
-    if ((rc = c->gh[2].ensure(std::max<size_t>(4, count * 8))) || (rc = c->io[2].ensure(std::max<size_t>(4, count * cw * 4))))
-        return rc;
-    if (r && (rc = c->io[1].ensure(std::max<size_t>(4, count * r_words * 4)))) return rc;
-    float *dg = (float *)c->gh[2].p, *dh = dg + count;
-    if (count) {
-        HIPOK(hipMemcpyAsync(dg, g, count * 4, hipMemcpyHostToDevice, c->stream));
-        HIPOK(hipMemcpyAsync(dh, h, count * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HostPipe pipe{c};
-    if (r) pipe.add_in(r, c->io[1].p, (size_t)r_words * 4);
-    pipe.add_out(out, c->io[2].p, cw * 4);
-    if ((rc = encrypt_gh_impl(k, c, dg, dh, count, r ? (const uint32_t *)c->io[1].p : nullptr, r_words, rng_seed,
-                              index0, (uint32_t *)c->io[2].p, flags, count ? &pipe : nullptr))) return rc;
-    return pipe.finish();
-}
-
-extern "C" int fthe_decrypt_gh_packed(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, float *g, float *h,
-                                      int64_t *g_code, int64_t *h_code, int short_pt) {
-    if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    const size_t cw = 2 * (size_t)k->n_words;
-    int rc;
-    // device outputs in one buffer: g codes, h codes, g floats, h floats
-    if ((rc = c->io[0].ensure(std::max<size_t>(4, count * cw * 4))) || (rc = c->gh[2].ensure(std::max<size_t>(8, count * 24))))
-        return rc;
-    int64_t *dgc = (int64_t *)c->gh[2].p, *dhc = dgc + count;
-    float *dg = (float *)(dhc + count), *dh = dg + count;
-    const GhOut o{dg, dh, dgc, dhc};
-    HostPipe pipe{c};
-    pipe.add_in(ct, c->io[0].p, cw * 4);
-    if ((rc = decrypt_impl(k, c, (const uint32_t *)c->io[0].p, count, nullptr, nullptr, count ? &pipe : nullptr,
-                           short_pt != 0, &o))) return rc;
-    if ((rc = pipe.finish())) return rc;
-    if (!count) return FTHE_OK;
-    if (g) HIPOK(hipMemcpy(g, dg, count * 4, hipMemcpyDeviceToHost));
-    if (h) HIPOK(hipMemcpy(h, dh, count * 4, hipMemcpyDeviceToHost));
-    if (g_code) HIPOK(hipMemcpy(g_code, dgc, count * 8, hipMemcpyDeviceToHost));
-    if (h_code) HIPOK(hipMemcpy(h_code, dhc, count * 8, hipMemcpyDeviceToHost));
-    return FTHE_OK;
-}
-
-// Host-resident slot-packed pairs: as the packed forms above, with rows = ceil(count / slots) ciphertexts (and
-// injected r) through the pipe and the count floats / codes in one copy each.
-extern "C" int fthe_encrypt_gh_slots(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
-                                     int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out,
-                                     int flags, int slots) {
-    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
-    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
-    if (rc) return rc;
-    if (r && (r_words <= 0 || r_words > ((flags & FTHE_ENC_FIXED_BASE_EXACT) ? 3 * (k->n_words + 2)
-                                         : k->n_words + ((flags & FTHE_ENC_FIXED_BASE) ? 4 : 0)))) return FTHE_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    const size_t cw = 2 * (size_t)k->n_words, rows = (count + slots - 1) / slots;
     if ((rc = c->gh[2].ensure(std::max<size_t>(4, count * 8))) || (rc = c->io[2].ensure(std::max<size_t>(4, rows * cw * 4))))
         return rc;
     if (r && (rc = c->io[1].ensure(std::max<size_t>(4, rows * r_words * 4)))) return rc;
@@ -4479,18 +4452,19 @@ extern "C" int fthe_encrypt_gh_slots(fthe_key *k, fthe_ctx *c, const float *g, c
     HostPipe pipe{c};
     if (r) pipe.add_in(r, c->io[1].p, (size_t)r_words * 4);
     pipe.add_out(out, c->io[2].p, cw * 4);
-    if ((rc = encrypt_gh_slots_impl(k, c, dg, dh, count, slot_bits, slots, r ? (const uint32_t *)c->io[1].p : nullptr,
-                                    r_words, rng_seed, (uint32_t *)c->io[2].p, flags, count ? &pipe : nullptr)))
+    if ((rc = impl(dg, dh, r ? (const uint32_t *)c->io[1].p : nullptr, (uint32_t *)c->io[2].p, count ? &pipe : nullptr)))
         return rc;
     return pipe.finish();
 }
 
-extern "C" int fthe_decrypt_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits,
-                                     float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt, int slots) {
-    int rc = decrypt_gh_slots_args(k, c, ct, count, slot_bits, short_pt, &slots);
-    if (rc) return rc;
+// The decrypt of rows ciphertexts into count pairs: impl(ct, GhOut, pipe) on the staged rows, then whichever of the
+// floats and codes the caller asked for.
+template <class Impl>
+static int decrypt_gh_host(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, size_t rows, float *g, float *h,
+                           int64_t *g_code, int64_t *h_code, Impl &&impl) {
     HIPOK(hipSetDevice(c->device));
-    const size_t cw = 2 * (size_t)k->n_words, rows = (count + slots - 1) / slots;
+    const size_t cw = 2 * (size_t)k->n_words;
+    int rc;
     // device outputs in one buffer: g codes, h codes, g floats, h floats
     if ((rc = c->io[0].ensure(std::max<size_t>(4, rows * cw * 4))) || (rc = c->gh[2].ensure(std::max<size_t>(8, count * 24))))
         return rc;
@@ -4498,8 +4472,7 @@ extern "C" int fthe_decrypt_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *c
     float *dg = (float *)(dhc + count), *dh = dg + count;
     HostPipe pipe{c};
     pipe.add_in(ct, c->io[0].p, cw * 4);
-    if ((rc = decrypt_gh_slots_impl(k, c, (const uint32_t *)c->io[0].p, count, slot_bits, slots,
-                                    GhOut{dg, dh, dgc, dhc}, short_pt != 0, count ? &pipe : nullptr))) return rc;
+    if ((rc = impl((const uint32_t *)c->io[0].p, GhOut{dg, dh, dgc, dhc}, count ? &pipe : nullptr))) return rc;
     if ((rc = pipe.finish())) return rc;
     if (!count) return FTHE_OK;
     if (g) HIPOK(hipMemcpy(g, dg, count * 4, hipMemcpyDeviceToHost));
@@ -4509,123 +4482,60 @@ extern "C" int fthe_decrypt_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *c
     return FTHE_OK;
 }
 
+extern "C" int fthe_encrypt_gh_packed(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                      const uint32_t *r, int r_words, uint64_t rng_seed, uint64_t index0,
+                                      uint32_t *out, int flags) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
+    if (!r_words_ok(k, r, r_words, flags)) return FTHE_ERR_ARG;
+    return encrypt_gh_host(k, c, g, h, count, count, r, r_words, out,
+                           [&](const float *dg, const float *dh, const uint32_t *dr, uint32_t *dout, HostPipe *pipe) {
+        return encrypt_gh_impl(k, c, dg, dh, count, dr, r_words, rng_seed, index0, dout, flags, pipe);
+    });
+}
+
+extern "C" int fthe_decrypt_gh_packed(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, float *g, float *h,
+                                      int64_t *g_code, int64_t *h_code, int short_pt) {
+    if (!k || !c || (!ct && count)) return FTHE_ERR_ARG;
+    return decrypt_gh_host(k, c, ct, count, count, g, h, g_code, h_code,
+                           [&](const uint32_t *dct, const GhOut &o, HostPipe *pipe) {
+        return decrypt_impl(k, c, dct, count, nullptr, nullptr, pipe, short_pt != 0, &o);
+    });
+}
+
+// Slot-packed pairs: rows = ceil(count / slots) ciphertexts for count pairs.
+extern "C" int fthe_encrypt_gh_slots(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count,
+                                     int slot_bits, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out,
+                                     int flags, int slots) {
+    if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    if (!r_words_ok(k, r, r_words, flags)) return FTHE_ERR_ARG;
+    return encrypt_gh_host(k, c, g, h, count, (count + slots - 1) / slots, r, r_words, out,
+                           [&](const float *dg, const float *dh, const uint32_t *dr, uint32_t *dout, HostPipe *pipe) {
+        return encrypt_gh_slots_impl(k, c, dg, dh, count, slot_bits, slots, dr, r_words, rng_seed, dout, flags, pipe);
+    });
+}
+
+extern "C" int fthe_decrypt_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, int slot_bits,
+                                     float *g, float *h, int64_t *g_code, int64_t *h_code, int short_pt, int slots) {
+    int rc = decrypt_gh_slots_args(k, c, ct, count, slot_bits, short_pt, &slots);
+    if (rc) return rc;
+    return decrypt_gh_host(k, c, ct, count, (count + slots - 1) / slots, g, h, g_code, h_code,
+                           [&](const uint32_t *dct, const GhOut &o, HostPipe *pipe) {
+        return decrypt_gh_slots_impl(k, c, dct, count, slot_bits, slots, o, short_pt != 0, pipe);
+    });
+}
+
 extern "C" int fthe_compress_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, int slot_bits,
                                       uint32_t *out, int slots) {
     if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
     int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
     if (rc) return rc;
-    HIPOK(hipSetDevice(c->device));
-    HostIO io{c}; void *dx, *dout;
     const size_t row = 2 * (size_t)k->n_words * 4, rows = (count + slots - 1) / slots;
-    if ((rc = io.in(0, x, count * row, &dx))) return rc;
-    if ((rc = io.outbuf(2, rows * row, &dout))) return rc;
-    if ((rc = fthe_compress_gh_slots_dev(k, c, (const uint32_t *)dx, count, slot_bits, (uint32_t *)dout, slots))) return rc;
-    return io.back(out, dout, rows * row);
-}
-
-// Staging buffers of the shared queues above this many bytes are released after their batch
-// (one large shared call must not pin a second copy of its ciphertexts for the key's lifetime).
-constexpr size_t kCoalesceKeepBytes = (size_t)64 << 20;
-template <class V> static void trim(V &v) {
-    if (v.capacity() * sizeof(typename V::value_type) > kCoalesceKeepBytes) { V().swap(v); }
-}
-
-// One leader runs everything pending (its own request included) as at most two batched calls
-// (full / short), then hands leadership to a caller still waiting.  A lone request runs straight
-// on the caller's buffers (no staging copy).
-static void coalesced_batch_impl(fthe_key *k, Coalescer *co, const std::vector<DecReq *> &batch) {
-    const size_t cw = 2 * (size_t)k->n_words, nw = k->n_words;
-    int rc0 = FTHE_OK;
-    if (!co->ctx) rc0 = fthe_ctx_create(k->device, &co->ctx);
-    if (batch.size() == 1) {
-        DecReq *r = batch[0];
-        r->rc = rc0 ? rc0 : decrypt_host(k, co->ctx, r->ct, r->count, r->m_low, r->m_full, r->short_pt);
-        return;
-    }
-    for (int kind = 0; kind < 2; kind++) {
-        size_t tot = 0;
-        bool want_full = false;
-        for (DecReq *r : batch)
-            if (r->short_pt == (kind == 1)) { tot += r->count; want_full |= r->m_full != nullptr; }
-        if (!tot) continue;
-        int rc = rc0;
-        if (!rc) {
-            co->ct.resize(tot * cw); co->lo.resize(tot);
-            if (want_full) co->full.resize(tot * nw);
-            size_t at = 0;
-            for (DecReq *r : batch)
-                if (r->short_pt == (kind == 1)) { memcpy(&co->ct[at * cw], r->ct, r->count * cw * 4); at += r->count; }
-            rc = decrypt_host(k, co->ctx, co->ct.data(), tot, co->lo.data(), want_full ? co->full.data() : nullptr,
-                              kind == 1);
-        }
-        size_t at = 0;
-        for (DecReq *r : batch) {
-            if (r->short_pt != (kind == 1)) continue;
-            r->rc = rc;
-            if (!rc) {
-                if (r->m_low) memcpy(r->m_low, &co->lo[at], r->count * 8);
-                if (r->m_full) memcpy(r->m_full, &co->full[at * nw], r->count * nw * 4);
-            }
-            at += r->count;
-        }
-    }
-    trim(co->ct); trim(co->lo); trim(co->full);
-}
-
-// Nothing may leave the C ABI by exception, and the leader must always mark its batch done and
-// hand over (fthe_decrypt_shared): allocation failures (staging vectors, copy threads) become
-// FTHE_ERR_NOMEM for every request of the batch.
-static void coalesced_batch(fthe_key *k, Coalescer *co, const std::vector<DecReq *> &batch) {
-    try {
-        coalesced_batch_impl(k, co, batch);
-    } catch (...) {
-        for (DecReq *r : batch) r->rc = FTHE_ERR_NOMEM;
-        try { trim(co->ct); trim(co->lo); trim(co->full); } catch (...) {}
-    }
-}
-
-// Encrypt side of the queue: requests grouped by flags, fresh device randomness per batch.
-static void coalesced_encrypt_impl(fthe_key *k, Coalescer *co, const std::vector<EncReq *> &batch) {
-    const size_t cw = 2 * (size_t)k->n_words;
-    int rc0 = FTHE_OK;
-    if (!co->ectx) rc0 = fthe_ctx_create(k->device, &co->ectx);
-    if (batch.size() == 1) {
-        EncReq *r = batch[0];
-        r->rc = rc0 ? rc0 : encrypt_host(k, co->ectx, r->m, 0, r->count, nullptr, 0, 0, r->out, r->flags);
-        return;
-    }
-    std::vector<int> kinds;
-    for (EncReq *r : batch)
-        if (std::find(kinds.begin(), kinds.end(), r->flags) == kinds.end()) kinds.push_back(r->flags);
-    for (int fl : kinds) {
-        size_t tot = 0;
-        for (EncReq *r : batch) if (r->flags == fl) tot += r->count;
-        int rc = rc0;
-        if (!rc) {
-            co->em.resize(tot); co->eout.resize(tot * cw);
-            size_t at = 0;
-            for (EncReq *r : batch)
-                if (r->flags == fl) { memcpy(&co->em[at], r->m, r->count * 8); at += r->count; }
-            rc = encrypt_host(k, co->ectx, co->em.data(), 0, tot, nullptr, 0, 0, co->eout.data(), fl);
-        }
-        size_t at = 0;
-        for (EncReq *r : batch) {
-            if (r->flags != fl) continue;
-            r->rc = rc;
-            if (!rc) memcpy(r->out, &co->eout[at * cw], r->count * cw * 4);
-            at += r->count;
-        }
-    }
-    trim(co->em); trim(co->eout);
-}
-
-static void coalesced_encrypt(fthe_key *k, Coalescer *co, const std::vector<EncReq *> &batch) {
-    try {
-        coalesced_encrypt_impl(k, co, batch);
-    } catch (...) {
-        for (EncReq *r : batch) r->rc = FTHE_ERR_NOMEM;
-        try { trim(co->em); trim(co->eout); } catch (...) {}
-    }
+    return host_in_out(c, x, count * row, out, rows * row, [&](const uint32_t *dx, uint32_t *dout) {
+        return fthe_compress_gh_slots_dev(k, c, dx, count, slot_bits, dout, slots);
+    });
 }
 
 static Coalescer *key_coalescer(fthe_key *k) {
@@ -4634,40 +4544,68 @@ static Coalescer *key_coalescer(fthe_key *k) {
     return k->co.get();
 }
 
-// Group commit with a linger.  The callers of a finished batch come back one at a time (each wakes from
-// notify_all, re-takes the mutex, returns, issues its next call), so a new leader that took the queue at
-// once would run a batch of one and leave the others to the round trip after: FedTree's OpenMP loops of
-// single-element calls (hist_tree_builder.cpp:574-591 through GHPair's operators; decrypt_gh per node,
-// FLtrainer.cpp:758-764) ran two launches per round.  A new leader waits until as many requests are pending
-// as there were callers in the previous round (its batch plus the requests that arrived while it ran), at
-// most FTHE_LINGER_US (default 200 us; 0: off) or a quarter of the previous batch's duration if that is
-// longer (a merged decrypt takes ~10 ms), the latter capped at kLingerCapUs so one huge batch (a bulk
-// add_shared of millions of rows) cannot make the next leader wait for callers that never come back; a lone
-// caller never waits.  Arrivals wake it when the count is reached.
-static constexpr int64_t kLingerCapUs = 3000;
-static int linger_us() {
-    static const int v = [] {
-        const char *e = getenv("FTHE_LINGER_US");
-        return e ? std::max(0, atoi(e)) : 200;
-    }();
-    return v;
+// The runners of the three queues (GroupCommit::submit's run_batch): the batch in groups that can share a call
+// (group_by_key), each gathered into the queue's staging vectors, run as one host-resident call on the queue's
+// context and scattered back, so an error reaches only its own group.  A lone decrypt or encrypt runs straight on
+// the caller's buffers (no staging copy).
+static void run_decrypts(fthe_key *k, Coalescer::Dec &q, const std::vector<DecReq *> &batch) {
+    TrimAfter<Coalescer::Dec> trim_after{q};
+    const size_t cw = 2 * (size_t)k->n_words, nw = k->n_words;
+    const int rc0 = q.context(k->device);
+    if (batch.size() == 1) {
+        DecReq *r = batch[0];
+        r->rc = rc0 ? rc0 : decrypt_host(k, q.ctx, r->ct, r->count, r->m_low, r->m_full, r->short_pt);
+        return;
+    }
+    for (const auto &grp : group_by_key(batch, [](const DecReq &r) { return r.short_pt; })) {
+        size_t tot = 0, at = 0;
+        bool want_full = false;
+        for (DecReq *r : grp.second) { tot += r->count; want_full |= r->m_full != nullptr; }
+        int rc = rc0;
+        if (!rc) {
+            q.ct.resize(tot * cw); q.lo.resize(tot);
+            if (want_full) q.full.resize(tot * nw);
+            for (DecReq *r : grp.second) { memcpy(&q.ct[at * cw], r->ct, r->count * cw * 4); at += r->count; }
+            rc = decrypt_host(k, q.ctx, q.ct.data(), tot, q.lo.data(), want_full ? q.full.data() : nullptr, grp.first);
+        }
+        at = 0;
+        for (DecReq *r : grp.second) {
+            r->rc = rc;
+            if (!rc) {
+                if (r->m_low) memcpy(r->m_low, &q.lo[at], r->count * 8);
+                if (r->m_full) memcpy(r->m_full, &q.full[at * nw], r->count * nw * 4);
+            }
+            at += r->count;
+        }
+    }
 }
-template <class Req>
-static void linger(Coalescer *co, std::unique_lock<std::mutex> &lk, const std::vector<Req *> &pend, size_t last,
-                   bool &lingering, int64_t last_us) {
-    if (last <= 1 || pend.size() >= last || linger_us() <= 0) return;
-    lingering = true;
-    // a quarter of a long batch (decrypts), capped: one huge batch must not make the next lone caller wait long
-    const int64_t bound = std::max<int64_t>(linger_us(), std::min<int64_t>(last_us / 4, kLingerCapUs));
-    co->lcv.wait_for(lk, std::chrono::microseconds(bound), [&] { return pend.size() >= last; });
-    lingering = false;
-}
-static int64_t us_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-}
-template <class Req>
-static void arrived(Coalescer *co, const std::vector<Req *> &pend, size_t last, bool lingering) {
-    if (lingering && pend.size() >= last) co->lcv.notify_all();
+
+// Encrypts grouped by flags, fresh device randomness per call.
+static void run_encrypts(fthe_key *k, Coalescer::Enc &q, const std::vector<EncReq *> &batch) {
+    TrimAfter<Coalescer::Enc> trim_after{q};
+    const size_t cw = 2 * (size_t)k->n_words;
+    const int rc0 = q.context(k->device);
+    if (batch.size() == 1) {
+        EncReq *r = batch[0];
+        r->rc = rc0 ? rc0 : encrypt_host(k, q.ctx, r->m, 0, r->count, nullptr, 0, 0, r->out, r->flags);
+        return;
+    }
+    for (const auto &grp : group_by_key(batch, [](const EncReq &r) { return r.flags; })) {
+        size_t tot = 0, at = 0;
+        for (EncReq *r : grp.second) tot += r->count;
+        int rc = rc0;
+        if (!rc) {
+            q.m.resize(tot); q.out.resize(tot * cw);
+            for (EncReq *r : grp.second) { memcpy(&q.m[at], r->m, r->count * 8); at += r->count; }
+            rc = encrypt_host(k, q.ctx, q.m.data(), 0, tot, nullptr, 0, 0, q.out.data(), grp.first);
+        }
+        at = 0;
+        for (EncReq *r : grp.second) {
+            r->rc = rc;
+            if (!rc) memcpy(r->out, &q.out[at * cw], r->count * cw * 4);
+            at += r->count;
+        }
+    }
 }
 
 extern "C" int fthe_decrypt_shared(fthe_key *k, const uint32_t *ct, size_t count, uint64_t *m_low, uint32_t *m_full,
@@ -4678,29 +4616,16 @@ extern "C" int fthe_decrypt_shared(fthe_key *k, const uint32_t *ct, size_t count
     Coalescer *co = key_coalescer(k);
     if (!co) return FTHE_ERR_NOMEM;
     DecReq r{ct, count, m_low, m_full, short_pt != 0};
-    std::unique_lock<std::mutex> lk(co->mu);
-    try { co->pending.push_back(&r); } catch (...) { return FTHE_ERR_NOMEM; }
-    arrived(co, co->pending, co->last, co->lingering);
-    for (;;) {
-        if (r.done) return r.rc;
-        if (!co->leader) {
-            co->leader = true;
-            linger(co, lk, co->pending, co->last, co->lingering, co->last_us);
-            std::vector<DecReq *> batch;
-            batch.swap(co->pending);                 // includes r
-            lk.unlock();
-            const auto t_batch = std::chrono::steady_clock::now();
-            coalesced_batch(k, co, batch);
-            co->last_us = us_since(t_batch);
-            lk.lock();
-            for (DecReq *q : batch) q->done = true;
-            co->last = batch.size() + co->pending.size();   // callers active in this round
-            co->leader = false;
-            co->cv.notify_all();
-            return r.rc;
-        }
-        co->cv.wait(lk);
-    }
+    return co->dec.submit(r, [&](const std::vector<DecReq *> &batch) { run_decrypts(k, co->dec, batch); });
+}
+
+extern "C" int fthe_encrypt_shared(fthe_key *k, const uint64_t *m, size_t count, uint32_t *out, int flags) {
+    if (!k || ((!m || !out) && count)) return FTHE_ERR_ARG;
+    if (!count) return FTHE_OK;
+    Coalescer *co = key_coalescer(k);
+    if (!co) return FTHE_ERR_NOMEM;
+    EncReq r{m, count, out, flags};
+    return co->enc.submit(r, [&](const std::vector<EncReq *> &batch) { run_encrypts(k, co->enc, batch); });
 }
 
 extern "C" int fthe_decrypt_short(fthe_key *k, fthe_ctx *c, const uint32_t *ct, size_t count, uint64_t *m_low,
@@ -4760,36 +4685,27 @@ extern "C" int fthe_sub_bits(fthe_key *k, fthe_ctx *c, const uint32_t *a, const 
 
 extern "C" int fthe_reduce_kway(fthe_key *k, fthe_ctx *c, const uint32_t *x, int kk, size_t count, uint32_t *out) {
     if (!k || !c || kk <= 0) return FTHE_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    HostIO io{c}; void *dx, *dout; int rc;
-    size_t bytes = count * 2 * (size_t)k->n_words * 4;
-    if ((rc = io.in(0, x, bytes * kk, &dx))) return rc;
-    if ((rc = io.outbuf(2, bytes, &dout))) return rc;
-    if ((rc = fthe_reduce_kway_dev(k, c, (const uint32_t *)dx, kk, count, (uint32_t *)dout))) return rc;
-    return io.back(out, dout, bytes);
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    return host_in_out(c, x, bytes * kk, out, bytes, [&](const uint32_t *dx, uint32_t *dout) {
+        return fthe_reduce_kway_dev(k, c, dx, kk, count, dout);
+    });
 }
 
 extern "C" int fthe_scalar_mul_u64(fthe_key *k, fthe_ctx *c, const uint32_t *x, uint64_t e, size_t count, uint32_t *out) {
     if (!k || !c) return FTHE_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    HostIO io{c}; void *dx, *dout; int rc;
-    size_t bytes = count * 2 * (size_t)k->n_words * 4;
-    if ((rc = io.in(0, x, bytes, &dx))) return rc;
-    if ((rc = io.outbuf(2, bytes, &dout))) return rc;
-    if ((rc = fthe_scalar_mul_u64_dev(k, c, (const uint32_t *)dx, e, count, (uint32_t *)dout))) return rc;
-    return io.back(out, dout, bytes);
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    return host_in_out(c, x, bytes, out, bytes, [&](const uint32_t *dx, uint32_t *dout) {
+        return fthe_scalar_mul_u64_dev(k, c, dx, e, count, dout);
+    });
 }
 
 extern "C" int fthe_scalar_mul_words(fthe_key *k, fthe_ctx *c, const uint32_t *x, const uint32_t *e, int e_words,
                                      size_t count, uint32_t *out) {
     if (!k || !c) return FTHE_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    HostIO io{c}; void *dx, *dout; int rc;
-    size_t bytes = count * 2 * (size_t)k->n_words * 4;
-    if ((rc = io.in(0, x, bytes, &dx))) return rc;
-    if ((rc = io.outbuf(2, bytes, &dout))) return rc;
-    if ((rc = fthe_scalar_mul_words_dev(k, c, (const uint32_t *)dx, e, e_words, count, (uint32_t *)dout))) return rc;
-    return io.back(out, dout, bytes);
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    return host_in_out(c, x, bytes, out, bytes, [&](const uint32_t *dx, uint32_t *dout) {
+        return fthe_scalar_mul_words_dev(k, c, dx, e, e_words, count, dout);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -4859,111 +4775,45 @@ extern "C" int fthe_decode_fixed_dev(fthe_ctx *c, const uint64_t *m, size_t coun
     return hipGetLastError() == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
 }
 
-extern "C" int fthe_encrypt_shared(fthe_key *k, const uint64_t *m, size_t count, uint32_t *out, int flags) {
-    if (!k || ((!m || !out) && count)) return FTHE_ERR_ARG;
-    if (!count) return FTHE_OK;
-    Coalescer *co = key_coalescer(k);
-    if (!co) return FTHE_ERR_NOMEM;
-    EncReq r{m, count, out, flags};
-    std::unique_lock<std::mutex> lk(co->mu);
-    try { co->epending.push_back(&r); } catch (...) { return FTHE_ERR_NOMEM; }
-    arrived(co, co->epending, co->elast, co->elingering);
-    for (;;) {
-        if (r.done) return r.rc;
-        if (!co->eleader) {
-            co->eleader = true;
-            linger(co, lk, co->epending, co->elast, co->elingering, co->elast_us);
-            std::vector<EncReq *> batch;
-            batch.swap(co->epending);                // includes r
-            lk.unlock();
-            const auto t_batch = std::chrono::steady_clock::now();
-            coalesced_encrypt(k, co, batch);
-            co->elast_us = us_since(t_batch);
-            lk.lock();
-            for (EncReq *q : batch) q->done = true;
-            co->elast = batch.size() + co->epending.size();   // callers active in this round
-            co->eleader = false;
-            co->cv.notify_all();
-            return r.rc;
-        }
-        co->cv.wait(lk);
-    }
-}
-
 // ---------------------------------------------------------------------------
 // Shared ciphertext add / scalar mul: GHPair::operator+, +=, - of the USE_HIP build
 // (common.h:150-337) call these once per GHPair from FedTree's OpenMP workers
 // (hist_tree_builder.cpp:574-591, 1031-1047); the key's third queue merges the concurrent
 // calls into one launch per operation kind (adds together, muls per exponent).  Inputs are
-// staged before any output is written, so out may alias a or b (fixes SURVEY Q11).
-static void coalesced_ops_impl(fthe_key *k, Coalescer *co, const std::vector<OpReq *> &batch) {
+// staged before any output is written, a lone request's too, so out may alias a or b (fixes SURVEY Q11).
+static void run_ops(fthe_key *k, Coalescer::Ops &q, const std::vector<OpReq *> &batch) {
+    TrimAfter<Coalescer::Ops> trim_after{q};
     const size_t cw = 2 * (size_t)k->n_words;
-    int rc0 = FTHE_OK;
-    if (!co->octx) rc0 = fthe_ctx_create(k->device, &co->octx);
-    // kinds: adds (mul == false), then one group per distinct exponent
-    std::vector<std::pair<bool, uint64_t>> kinds;
-    for (OpReq *r : batch) {
-        std::pair<bool, uint64_t> kd{r->mul, r->mul ? r->k : 0};
-        if (std::find(kinds.begin(), kinds.end(), kd) == kinds.end()) kinds.push_back(kd);
-    }
-    for (const auto &kd : kinds) {
-        size_t tot = 0;
-        for (OpReq *r : batch) if (r->mul == kd.first && (!kd.first || r->k == kd.second)) tot += r->count;
+    const int rc0 = q.context(k->device);
+    for (const auto &grp : group_by_key(batch, [](const OpReq &r) { return std::make_pair(r.mul, r.mul ? r.k : 0); })) {
+        const bool mul = grp.first.first;
+        size_t tot = 0, at = 0;
+        for (OpReq *r : grp.second) tot += r->count;
         int rc = rc0;
         if (!rc) {
-            co->oa.resize(tot * cw); co->oout.resize(tot * cw);
-            if (!kd.first) co->ob.resize(tot * cw);
-            size_t at = 0;
-            for (OpReq *r : batch) {
-                if (r->mul != kd.first || (kd.first && r->k != kd.second)) continue;
-                memcpy(&co->oa[at * cw], r->a, r->count * cw * 4);
-                if (!kd.first) memcpy(&co->ob[at * cw], r->b, r->count * cw * 4);
+            q.a.resize(tot * cw); q.out.resize(tot * cw);
+            if (!mul) q.b.resize(tot * cw);
+            for (OpReq *r : grp.second) {
+                memcpy(&q.a[at * cw], r->a, r->count * cw * 4);
+                if (!mul) memcpy(&q.b[at * cw], r->b, r->count * cw * 4);
                 at += r->count;
             }
-            rc = kd.first ? fthe_scalar_mul_u64(k, co->octx, co->oa.data(), kd.second, tot, co->oout.data())
-                          : fthe_add(k, co->octx, co->oa.data(), co->ob.data(), tot, co->oout.data());
+            rc = mul ? fthe_scalar_mul_u64(k, q.ctx, q.a.data(), grp.first.second, tot, q.out.data())
+                     : fthe_add(k, q.ctx, q.a.data(), q.b.data(), tot, q.out.data());
         }
-        size_t at = 0;
-        for (OpReq *r : batch) {
-            if (r->mul != kd.first || (kd.first && r->k != kd.second)) continue;
+        at = 0;
+        for (OpReq *r : grp.second) {
             r->rc = rc;
-            if (!rc) memcpy(r->out, &co->oout[at * cw], r->count * cw * 4);
+            if (!rc) memcpy(r->out, &q.out[at * cw], r->count * cw * 4);
             at += r->count;
         }
     }
-    trim(co->oa); trim(co->ob); trim(co->oout);
 }
 
 static int op_shared(fthe_key *k, OpReq &r) {
     Coalescer *co = key_coalescer(k);
     if (!co) return FTHE_ERR_NOMEM;
-    std::unique_lock<std::mutex> lk(co->mu);
-    try { co->opending.push_back(&r); } catch (...) { return FTHE_ERR_NOMEM; }
-    arrived(co, co->opending, co->olast, co->olingering);
-    for (;;) {
-        if (r.done) return r.rc;
-        if (!co->oleader) {
-            co->oleader = true;
-            linger(co, lk, co->opending, co->olast, co->olingering, co->olast_us);
-            std::vector<OpReq *> batch;
-            batch.swap(co->opending);                // includes r
-            lk.unlock();
-            try {
-                const auto t_batch = std::chrono::steady_clock::now();
-                coalesced_ops_impl(k, co, batch);
-                co->olast_us = us_since(t_batch);
-            } catch (...) {
-                for (OpReq *q : batch) q->rc = FTHE_ERR_NOMEM;
-            }
-            lk.lock();
-            for (OpReq *q : batch) q->done = true;
-            co->olast = batch.size() + co->opending.size();   // callers active in this round
-            co->oleader = false;
-            co->cv.notify_all();
-            return r.rc;
-        }
-        co->cv.wait(lk);
-    }
+    return co->ops.submit(r, [&](const std::vector<OpReq *> &batch) { run_ops(k, co->ops, batch); });
 }
 
 extern "C" int fthe_add_shared(fthe_key *k, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out) {

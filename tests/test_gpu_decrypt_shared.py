@@ -180,3 +180,67 @@ def test_add_mul_shared_many_threads_alias_safe(pl):
         want_back = pl.add_batch(res[i][0], pl.scalar_mul(cts[a["j"]][None], 2**64 - 1))
         assert np.array_equal(res[i][1], want_back), i
         assert int(pl.decrypt_u64(res[i][1])[0]) == gold["cases"][a["i"]]["m"] % 2**64
+
+
+def test_ops_batch_with_several_kinds(pl):
+    """One batch of the ops queue with adds and scalar muls of three exponents: 16 threads behind one
+    barrier, adds and muls alternating by thread; every caller gets the batch engine's result bit for bit
+    (the queue groups adds together and muls per exponent)."""
+    T, exps = 16, (3, 2**64 - 1, 2**32 + 1)
+    rng = np.random.default_rng(17)
+    rows = pl.encrypt_u64(rng.integers(0, 2**64, 2 * T, dtype=np.uint64), seed=31)
+    res, bad = [None] * T, []
+    go = threading.Barrier(T)
+
+    def work(i):
+        try:
+            go.wait()
+            if i % 2 == 0:
+                res[i] = pl.add_shared(rows[i:i + 1], rows[T + i:T + i + 1])
+            else:
+                res[i] = pl.scalar_mul_shared(rows[i:i + 1], exps[(i // 2) % 3])
+        except Exception as e:  # noqa: BLE001
+            bad.append((i, repr(e)))
+
+    _run_all(work, T)
+    assert not bad, bad
+    for i in range(T):
+        want = pl.add_batch(rows[i:i + 1], rows[T + i:T + i + 1]) if i % 2 == 0 \
+            else pl.scalar_mul(rows[i:i + 1], exps[(i // 2) % 3])
+        assert np.array_equal(res[i], want), i
+
+
+def test_host_encrypt_forms_bound_r_words(pl):
+    """fthe_encrypt_u64, fthe_encrypt_gh_packed and fthe_encrypt_gh_slots bound the words of injected
+    randomness per ciphertext alike: 1..n_words, n_words + 4 with FTHE_ENC_FIXED_BASE, 3 (n_words + 2) with
+    FTHE_ENC_FIXED_BASE_EXACT; outside that FTHE_ERR_ARG.  r_words = n_words encrypts."""
+    from fedtree_amd import _lib
+    from fedtree_amd.paillier import _ptr, encode_fixed
+    nw, cw, slot_bits = pl.n_words, 2 * pl.n_words, 224
+    rng = np.random.default_rng(23)
+    r = np.zeros((1, 3 * (nw + 2) + 1), dtype=np.uint32)
+    r[0, :nw - 1] = rng.integers(0, 2**32, nw - 1, dtype=np.uint64).astype(np.uint32)    # below n, nonzero
+    m = np.array([0x123456789ABCDEF0], dtype=np.uint64)
+    g, h = np.array([0.5], dtype=np.float32), np.array([-0.25], dtype=np.float32)
+    out = np.zeros((1, cw), dtype=np.uint32)
+    key, ctx = pl._key, pl.dev.ctx
+    forms = {
+        "u64": lambda rw, fl: pl.lib.fthe_encrypt_u64(key, ctx, _ptr(m), 1, _ptr(r), rw, 0, _ptr(out), fl),
+        "gh_packed": lambda rw, fl: pl.lib.fthe_encrypt_gh_packed(key, ctx, _ptr(g), _ptr(h), 1, _ptr(r), rw, 0, 0,
+                                                                  _ptr(out), fl),
+        "gh_slots": lambda rw, fl: pl.lib.fthe_encrypt_gh_slots(key, ctx, _ptr(g), _ptr(h), 1, slot_bits, _ptr(r), rw,
+                                                                0, _ptr(out), fl, 0),
+    }
+    codes = (encode_fixed(g).view(np.int64), encode_fixed(h).view(np.int64))
+    for name, call in forms.items():
+        for rw, fl in ((0, 0), (nw + 1, 0), (nw + 5, _lib.FTHE_ENC_FIXED_BASE),
+                       (3 * (nw + 2) + 1, _lib.FTHE_ENC_FIXED_BASE_EXACT)):
+            assert call(rw, fl) == _lib.FTHE_ERR_ARG, (name, rw, fl)
+        out[:] = 0
+        assert call(nw, 0) == 0, name
+        if name == "u64":
+            assert np.array_equal(pl.decrypt_u64(out), m)
+            continue
+        got = pl.decrypt_gh_packed(out, codes=True) if name == "gh_packed" \
+            else pl.decrypt_gh_slots(out, 1, slot_bits, codes=True)
+        assert all(np.array_equal(a, b) for a, b in zip(got[2:], codes)), name
