@@ -128,6 +128,10 @@ _PROTOS = {
     "fthe_decrypt_gh_packed": (_I, [_P, _P, _P, _SZ, _P, _P, _P, _P, _I]),
     "fthe_sub_bits_dev": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
     "fthe_sub_bits": (_I, [_P, _P, _P, _P, _SZ, _I, _P]),
+    "fthe_invert_dev": (_I, [_P, _P, _P, _SZ, _P]),
+    "fthe_invert": (_I, [_P, _P, _P, _SZ, _P]),
+    "fthe_sub_inv_dev": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _P]),
+    "fthe_sub_inv": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _P]),
     "fthe_gh_slots": (_I, [_P, _I, _I]),
     "fthe_pack_gh_slots_dev": (_I, [_P, _P, _P, _SZ, _I, _I, _P]),
     "fthe_unpack_gh_slots_dev": (_I, [_P, _P, _I, _SZ, _I, _I, _P, _P, _P, _P]),

@@ -88,6 +88,8 @@ def build_kernels():
                     lambda: gen_nadicb.gen_nadicb("fthe_nadic_b76", nadicb_waves, nadicb_dbg)))
     # the P-2048 ciphertext add with a matrix-core Barrett reduction (not an op-program kernel): blob 3152
     kernels.append((3152, "fthe_addb_q152", "addb_q152", lambda: gen_addb.gen_addb("fthe_addb_q152", addb_dbg)))
+    # its paired entry point (x y and x y2 in one launch, x unpacked once: the batched inverse's down step): blob 3153
+    kernels.append((3153, "fthe_addb_pair", "addb_pair", lambda: gen_addb.gen_addb("fthe_addb_pair", "pair")))
     for S, name, stem, make in kernels:
         asm = os.path.join(GEN, f"{stem}.s")
         src = make()

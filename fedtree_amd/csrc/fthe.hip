@@ -77,6 +77,8 @@ const Shape kVariants[MAX_VARIANTS] = {{37, 28, 1}, {74, 28, 1}, {152, 27, 4}, {
                                        {kPadicMfmaTS, 28, 1}, {kPadicMfmaSS, 28, 1}, {kPadicMfmaLS, 28, 1},
                                        {kPadicMfmaKS, 28, 1}};
 constexpr Shape kLatShape{80, 27, 4};
+constexpr int kAddbPairBlob = 3153;       // fthe_addb_pair (gen_addb.py, switch pair): 8 waves per workgroup
+constexpr int kAddbPairWaves = 8;
 constexpr int kAddbBlob = 3152;           // fthe_addb_q152's code object in gen/montprog_blobs.h
 
 int variant_index(int S) {
@@ -288,6 +290,8 @@ struct fthe_ctx {
     hipFunction_t fn[MAX_VARIANTS] = {};
     hipModule_t mod_addb = nullptr;           // fthe_addb_q152 (gen_addb.py): P-2048 adds, matrix-core Barrett
     hipFunction_t fn_addb = nullptr;
+    hipModule_t mod_addb_pair = nullptr;      // fthe_addb_pair: x y and x y2 in one launch (the batched inverse)
+    hipFunction_t fn_addb_pair = nullptr;
     DevBuf slots, slots1, scratch, io[5];   // slots1: the small-modulus (mod p, q) programs
     size_t mem_limit = 0;                   // fthe_ctx_set_mem_limit: cap on the slot region grown for a call
     DevBuf hb[6];                           // histogram CSR / segmented-product plan (device)
@@ -295,6 +299,7 @@ struct fthe_ctx {
     DevBuf dec[3];                          // decimal codec: 9-digit chunks, lengths, leading chunk / error flag
     DevBuf gh[3];                           // packed / slot-packed pairs: plaintext words of an encrypt, one decrypt
                                             // chunk's plaintext words, the host forms' floats / codes
+    PinBuf inv_top;                         // batched inverse: every chunk's top rows, to the host and back
     void *cub_tmp = nullptr; size_t cub_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_mm = 0;
@@ -614,6 +619,10 @@ extern "C" int fthe_ctx_create(int device, fthe_ctx **out) {
         HIPOK(hipModuleLoadData(&c->mod_addb, blob));
         HIPOK(hipModuleGetFunction(&c->fn_addb, c->mod_addb, "fthe_addb_q152"));
     }
+    if (const unsigned char *blob = fthe_montprog_blob(kAddbPairBlob)) {
+        HIPOK(hipModuleLoadData(&c->mod_addb_pair, blob));
+        HIPOK(hipModuleGetFunction(&c->fn_addb_pair, c->mod_addb_pair, "fthe_addb_pair"));
+    }
     HIPOK(hipEventCreate(&c->ev0));
     HIPOK(hipEventCreate(&c->ev1));
     HIPOK(hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -641,6 +650,7 @@ extern "C" void fthe_ctx_destroy(fthe_ctx *c) {
     if (c->side) (void)hipStreamSynchronize(c->side);
     for (int i = 0; i < MAX_VARIANTS; i++) if (c->mod[i]) (void)hipModuleUnload(c->mod[i]);
     if (c->mod_addb) (void)hipModuleUnload(c->mod_addb);
+    if (c->mod_addb_pair) (void)hipModuleUnload(c->mod_addb_pair);
     if (c->cub_tmp) (void)hipFree(c->cub_tmp);
     for (auto &e : c->prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -3542,6 +3552,25 @@ static int launch_addb(fthe_ctx *c, const fthe_key *k, const uint32_t *x, const 
     return FTHE_OK;
 }
 
+// out = x y and out2 = x y2 mod n^2 for count (at most 4M) rows on fthe_addb_pair: x is loaded and unpacked once per
+// batch of 16 rows.  A batch reads its rows of x, y, then writes out, then reads y2, then writes out2, so out2 may be
+// y (not out = y2).
+static int launch_addb_pair(fthe_ctx *c, const fthe_key *k, const uint32_t *x, const uint32_t *y, uint32_t *out,
+                            const uint32_t *y2, uint32_t *out2, size_t count) {
+    if (count == 0) return FTHE_OK;
+    const size_t per_wg = 16 * (size_t)kAddbPairWaves;
+    const unsigned blocks = (unsigned)std::min<size_t>((count + per_wg - 1) / per_wg, (size_t)c->n_cu);
+    struct { const void *x, *y; void *o; const void *kc; uint32_t count, nwg; const void *xi, *yi, *y2; void *o2; }
+        args = {x, y, out, k->d_addb, (uint32_t)count, blocks, nullptr, nullptr, y2, out2};
+    static_assert(sizeof(args) == 72, "kernarg layout of gen_addb.py, switch pair");
+    size_t sz = sizeof(args);
+    void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    if (hipModuleLaunchKernel(c->fn_addb_pair, blocks, 1, 1, 64 * kAddbPairWaves, 1, 1, 0, c->stream, nullptr, cfg) !=
+        hipSuccess)
+        return FTHE_ERR_HIP;
+    return FTHE_OK;
+}
+
 // Test hook (include/fthe.h): the per-key context bytes of fthe_addb_q152, host only.
 extern "C" int fthe_debug_addb_image(const uint32_t *n, int n_words, uint8_t *out, size_t cap, size_t *len) {
     if (!n || n_words <= 0 || !len) return FTHE_ERR_ARG;
@@ -3884,6 +3913,208 @@ extern "C" int fthe_add_mont_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, co
                                  uint32_t *out) {
     const uint32_t *xs[2] = {a, b};
     return rowprod_impl(k, c, xs, 2, count, out, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Batched modular inverse (Montgomery's trick): fthe_invert_dev / fthe_sub_inv_dev
+//
+// One tree per chunk of m rows x.  Level l has m_l rows (m_0 = m, m_{l+1} = ceil(m_l / 2)) and pairs row i with
+// row i + h, h = ceil(m_l / 2); an odd level's row h - 1 passes through:
+//   up:    P_{l+1}[i] = P_l[i] P_l[i + h]                       (P_0 = x)
+//   top:   P_t, at most kInvTop rows, goes to the host: I_t[j] = P_t[j]^-1 (1 + offset n) by GMP
+//   down:  I_l[i] = I_{l+1}[i] P_l[i + h],  I_l[i + h] = I_{l+1}[i] P_l[i];  the last level also multiplies by a.
+// Every step is a product of contiguous row ranges (InvTree::mul): about 1 product per row up, 1 down to level 1,
+// 1 at level 0 and 1 more for a.  Workspace (c->scratch): A, m + 64 rows, holds P_1 .. P_t one after another and,
+// at the last level, the two halves of x's inverses before anything goes to out (out may be x, a or b); B, two
+// halves of ceil(m / 2) + kInvTop rows, holds I_{l+1} and I_l in turn.
+namespace {
+constexpr size_t kInvTop = 4;
+// Rows per tree; FTHE_INV_CHUNK overrides (A/B, chunk-boundary tests).  Capped by launch_addb's 4M rows per launch
+// and by fthe_ctx_set_mem_limit (the workspace is two rows per row).
+size_t inv_chunk_rows() {
+    static const size_t v = [] {
+        const char *e = getenv("FTHE_INV_CHUNK");
+        size_t c = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 20;
+        return std::min(std::max<size_t>(c, 1), (size_t)1 << 22);
+    }();
+    return v;
+}
+constexpr size_t inv_ws_rows(size_t m) { return m + 64 + 2 * ((m + 1) / 2 + kInvTop); }
+
+struct InvTree {
+    fthe_key *k; fthe_ctx *c; Launch Lc; size_t cw;
+    uint32_t *A = nullptr, *B[2] = {};
+    std::vector<size_t> ms;                 // rows of level 0 .. t
+    std::vector<uint32_t *> P;              // P_1 .. P_t in A (P[0]: the chunk's x)
+
+    // out = x y mod n^2 over cnt contiguous rows; out may be exactly x or y.
+    int mul(const uint32_t *x, const uint32_t *y, uint32_t *out, size_t cnt) {
+        if (!cnt) return FTHE_OK;
+        if (k->d_addb && c->fn_addb) {
+            Lc.mm += (double)cnt;
+            return launch_addb(c, k, x, y, out, cnt);
+        }
+        const int S = Lc.S, L = Lc.L;
+        for (size_t off = 0; off < cnt; off += L) {
+            const size_t n = std::min((size_t)L, cnt - off);
+            Lc.live = n;
+            int rc;
+            if (k->rowio) {
+                const void *rows[3] = {x + off * cw, y + off * cw, out + off * cw};
+                if ((rc = Lc.prog(k->pr_add_w, k->mn2, rows, 3))) return rc;
+            } else {
+                pack_rows(c->stream, x + off * cw, (int)cw, n, 0, Lc.slot(SL_IN0), S, L, Lc.B);
+                pack_rows(c->stream, y + off * cw, (int)cw, n, 0, Lc.slot(SL_IN1), S, L, Lc.B);
+                if ((rc = Lc.prog(k->pr_add, k->mn2))) return rc;
+                unpack_rows(c->stream, Lc.slot(SL_OUTP), k->cst(k->c_n2), S, L, n, out + off * cw, (int)cw, Lc.B);
+            }
+        }
+        return FTHE_OK;
+    }
+    // o1 = x y and o2 = x y2 over cnt rows: one paired launch at a 2048-bit n (FTHE_INV_NO_PAIR=1: the two adds)
+    int mul2(const uint32_t *x, const uint32_t *y, uint32_t *o1, const uint32_t *y2, uint32_t *o2, size_t cnt) {
+        if (!cnt) return FTHE_OK;
+        if (k->d_addb && c->fn_addb_pair && cnt <= ((size_t)1 << 22) && !getenv("FTHE_INV_NO_PAIR")) {
+            Lc.mm += 2 * (double)cnt;
+            return launch_addb_pair(c, k, x, y, o1, y2, o2, cnt);
+        }
+        if (int rc = mul(x, y, o1, cnt)) return rc;
+        return mul(x, y2, o2, cnt);
+    }
+    int copy(uint32_t *dst, const uint32_t *src, size_t rows) {
+        if (rows && dst != src)
+            HIPOK(hipMemcpyAsync(dst, src, rows * cw * 4, hipMemcpyDeviceToDevice, c->stream));
+        return FTHE_OK;
+    }
+    uint32_t *I(size_t l) const { return B[l & 1 ? 0 : 1]; }
+
+    void shape(const uint32_t *x, size_t m) {
+        ms.assign(1, m);
+        P.assign(1, const_cast<uint32_t *>(x));
+        uint32_t *next = A;
+        while (ms.back() > kInvTop) {
+            const size_t h = (ms.back() + 1) / 2;
+            ms.push_back(h);
+            P.push_back(next);
+            next += h * cw;
+        }
+    }
+    // Up-sweep of the chunk x (m rows); the top level's rows arrive in `top` (pinned) after the stream is drained.
+    int up(const uint32_t *x, size_t m, uint32_t *top, bool fetch) {
+        shape(x, m);
+        int rc;
+        for (size_t l = 0; l + 1 < ms.size(); l++) {
+            const size_t h = ms[l + 1], f = ms[l] / 2;
+            if ((rc = mul(P[l], P[l] + h * cw, P[l + 1], f))) return rc;
+            if (ms[l] & 1 && (rc = copy(P[l + 1] + (h - 1) * cw, P[l] + (h - 1) * cw, 1))) return rc;
+        }
+        if (!fetch) return FTHE_OK;
+        HIPOK(hipMemcpyAsync(top, P.back(), ms.back() * cw * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        return FTHE_OK;
+    }
+    // top: the rows P_t -> their inverses times cfac, in place (host).  FTHE_ERR_ARG: a row of the chunk is no unit.
+    int invert_top(uint32_t *top, const mpz_t cfac) const {
+        const size_t T = ms.back();
+        std::vector<Mpz> r(T), pre(T);
+        for (size_t j = 0; j < T; j++) {
+            mpz_from_words(r[j], top + j * cw, (int)cw);
+            if (j) { mpz_mul(pre[j], pre[j - 1], r[j]); mpz_mod(pre[j], pre[j], k->n2); }
+            else mpz_mod(pre[0], r[0], k->n2);
+        }
+        Mpz inv, t;
+        if (!mpz_invert(inv, pre[T - 1], k->n2)) return FTHE_ERR_ARG;
+        if (cfac) { mpz_mul(inv, inv, cfac); mpz_mod(inv, inv, k->n2); }
+        for (size_t j = T; j-- > 0;) {
+            if (j) { mpz_mul(t, inv, pre[j - 1]); mpz_mod(t, t, k->n2); }
+            else mpz_set(t, inv);
+            mpz_to_words(t, top + j * cw, (int)cw);
+            mpz_mul(inv, inv, r[j]); mpz_mod(inv, inv, k->n2);
+        }
+        return FTHE_OK;
+    }
+    // Down-sweep from the inverted top (pinned host rows); a == nullptr: out = x^-1, else out = a x^-1.
+    int down(const uint32_t *top, const uint32_t *a, uint32_t *out) {
+        const size_t t = ms.size() - 1, m = ms[0];
+        const uint32_t *x = P[0];
+        int rc;
+        HIPOK(hipMemcpyAsync(I(t), top, ms[t] * cw * 4, hipMemcpyHostToDevice, c->stream));
+        if (t == 0) return a ? mul(I(0), a, out, m) : copy(out, I(0), m);
+        for (size_t l = t - 1; l >= 1; l--) {
+            const size_t h = ms[l + 1], f = ms[l] / 2;
+            if ((rc = mul2(I(l + 1), P[l] + h * cw, I(l), P[l], I(l) + h * cw, f))) return rc;
+            if (ms[l] & 1 && (rc = copy(I(l) + (h - 1) * cw, I(l + 1) + (h - 1) * cw, 1))) return rc;
+        }
+        // level 0: every read of x is queued before the first write to out; P_1 .. P_t are spent, A is free
+        const size_t h = ms[1], f = m / 2;
+        uint32_t *lo = A, *hi = A + h * cw;
+        if ((rc = mul2(I(1), x + h * cw, lo, x, a ? hi : out + h * cw, f))) return rc;
+        if (m & 1 && (rc = copy(lo + (h - 1) * cw, I(1) + (h - 1) * cw, 1))) return rc;
+        if (!a) return copy(out, lo, h);
+        if ((rc = mul(lo, a, out, h))) return rc;
+        return mul(hi, a + h * cw, out + h * cw, f);
+    }
+};
+}  // namespace
+
+// a == nullptr: the inverse alone.  Several chunks: every chunk's up-sweep and host inversion runs before any chunk's
+// down-sweep (a non-unit fails the call with out untouched), so each chunk's up-sweep runs twice.
+static int invert_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *x, size_t count,
+                       const uint32_t *offset, int offset_words, uint32_t *out) {
+    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    if (offset_words < 0 || offset_words > k->n_words) return FTHE_ERR_ARG;
+    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    InvTree T{k, c};
+    T.cw = 2 * (size_t)k->n_words;
+    const size_t row = T.cw * 4;
+    size_t chunk = std::min(inv_chunk_rows(), std::max<size_t>(count, 1));
+    if (c->mem_limit && inv_ws_rows(chunk) * row > c->mem_limit && inv_ws_rows(chunk) * row > c->scratch.n) {
+        const size_t fit = c->mem_limit / row;          // rows of workspace the limit admits
+        if (fit < inv_ws_rows(1)) return FTHE_ERR_NOMEM;
+        chunk = std::min(chunk, (fit - inv_ws_rows(0)) / 2 + 1);     // two rows per row: at most one too many
+        while (inv_ws_rows(chunk) > fit) chunk--;
+    }
+    // (the matrix-core add reads and writes rows only: no slot region to speak of)
+    const bool addb = k->d_addb && c->fn_addb;
+    int rc = k->rowio ? begin_call(c, k, addb ? 1 : chunk, T.Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
+                      : begin_call(c, k, chunk, T.Lc, nslots_for(k), k->sn2);
+    if (rc) return rc;
+    if (count == 0) return end_call(c, T.Lc);
+    const size_t nch = (count + chunk - 1) / chunk, top_words = kInvTop * T.cw;
+    if ((rc = c->scratch.ensure(inv_ws_rows(chunk) * row)) || (rc = c->inv_top.ensure(nch * top_words * 4))) return rc;
+    T.A = (uint32_t *)c->scratch.p;
+    T.B[0] = T.A + (chunk + 64) * T.cw;
+    T.B[1] = T.B[0] + ((chunk + 1) / 2 + kInvTop) * T.cw;
+    if (!addb && (!k->rowio || !k->add_classical)) T.Lc.fill(SL_C0, k->c_R2n2);
+    Mpz cfac;
+    const bool shifted = offset && offset_words > 0;
+    if (shifted) {
+        mpz_from_words(cfac, offset, offset_words);
+        mpz_mul(cfac, cfac, k->n); mpz_add_ui(cfac, cfac, 1); mpz_mod(cfac, cfac, k->n2);
+    }
+    uint32_t *tops = (uint32_t *)c->inv_top.p;
+    for (size_t j = 0; j < nch; j++) {
+        const size_t off = j * chunk, m = std::min(chunk, count - off);
+        if ((rc = T.up(x + off * T.cw, m, tops + j * top_words, true))) return rc;
+        if ((rc = T.invert_top(tops + j * top_words, shifted ? (mpz_srcptr)cfac : nullptr))) return rc;
+        if (nch == 1 && (rc = T.down(tops, a, out))) return rc;
+    }
+    for (size_t j = 0; nch > 1 && j < nch; j++) {
+        const size_t off = j * chunk, m = std::min(chunk, count - off);
+        if ((rc = T.up(x + off * T.cw, m, nullptr, false))) return rc;
+        if ((rc = T.down(tops + j * top_words, a ? a + off * T.cw : nullptr, out + off * T.cw))) return rc;
+    }
+    return end_call(c, T.Lc);
+}
+
+extern "C" int fthe_invert_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, uint32_t *out) {
+    return invert_impl(k, c, nullptr, x, count, nullptr, 0, out);
+}
+
+extern "C" int fthe_sub_inv_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count,
+                                const uint32_t *offset, int offset_words, uint32_t *out) {
+    if (!a && count) return FTHE_ERR_ARG;
+    return invert_impl(k, c, a, b, count, offset, offset_words, out);
 }
 
 // Gathered K-way products: out[g] = prod_{j<K} x[idx[j*G + g]] mod n^2 (idx < 0 -> 1),
@@ -4681,6 +4912,27 @@ extern "C" int fthe_sub_bits(fthe_key *k, fthe_ctx *c, const uint32_t *a, const 
                              uint32_t *out) {
     if (bits <= 0) return FTHE_ERR_ARG;
     return pair_host(k, c, a, b, count, out, bits);
+}
+
+extern "C" int fthe_invert(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, uint32_t *out) {
+    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    return host_in_out(c, x, bytes, out, bytes, [&](const uint32_t *dx, uint32_t *dout) {
+        return fthe_invert_dev(k, c, dx, count, dout);
+    });
+}
+
+// A failed call (a non-unit row) returns before the copy back: the caller's out stays as it was.
+extern "C" int fthe_sub_inv(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count,
+                            const uint32_t *offset, int offset_words, uint32_t *out) {
+    if (!k || !c || ((!a || !b || !out) && count)) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    HostIO io{c}; void *da, *db, *dout; int rc;
+    if ((rc = io.in(0, a, bytes, &da)) || (rc = io.in(1, b, bytes, &db)) || (rc = io.outbuf(2, bytes, &dout))) return rc;
+    if ((rc = fthe_sub_inv_dev(k, c, (const uint32_t *)da, (const uint32_t *)db, count, offset, offset_words,
+                               (uint32_t *)dout))) return rc;
+    return io.back(out, dout, bytes);
 }
 
 extern "C" int fthe_reduce_kway(fthe_key *k, fthe_ctx *c, const uint32_t *x, int kk, size_t count, uint32_t *out) {

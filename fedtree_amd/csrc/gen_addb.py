@@ -41,6 +41,7 @@ idx[g] < 0 the integer 1: the gathered products of the histogram scatter / segme
 kctx: the LDS image (IMG_BYTES: mu copies, N copies, corrections), then N as 128 dwords, then the row 1.
 """
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -149,7 +150,7 @@ CHUNKS = [list(range(0, 8)), list(range(8, 16)), list(range(16, 24)), list(range
 # cost some overlap).  Correct schedules: nokara, nocnd, mfz (below); slowall: every lane through the
 # normalisation's slow path (the emulator's test build).
 SWITCHES = ("noprod", "nomfma", "nonorm", "nobarrett", "nocanon", "ldsfree", "stamp", "slowall", "nocnd", "nokara",
-            "mfz", "mznorm", "mzmfma")
+            "mfz", "mznorm", "mzmfma", "pair")
 
 
 def parse_dbg(dbg):
@@ -161,8 +162,19 @@ KARGS = tuple((8 * i, 8, 'global_buffer') for i in range(4)) + ((32, 4, 'by_valu
                                                                 (40, 8, 'global_buffer'), (48, 8, 'global_buffer'))
 
 
+PAIR_WAVES = 8                   # the paired entry point: 206 VGPRs, two waves per SIMD
+PAIR_KARGS = KARGS + ((56, 8, 'global_buffer'), (64, 8, 'global_buffer'))
+
+
 def gen_addb(name: str, dbg="") -> str:
     DBG = parse_dbg(dbg)
+    # "pair" (a correct schedule, the entry point fthe_addb_pair): out[g] = x[g] y[g] and out2[g] = x[g] y2[g] in one
+    # launch -- the down step of the batched inverse.  x is loaded and unpacked once per batch: its 38
+    # limbs wait in v168..v205 while the first product runs, which costs the third wave per SIMD.  The batch body is
+    # emitted twice (the second time with its labels renamed, x's load and unpack replaced by the copy back, and
+    # s[6:7] / s[8:9] pointing at y2 / out2: kernarg 56 and 64).  Direct rows only (both index lists null).
+    PAIR = "pair" in DBG
+    NW = PAIR_WAVES if PAIR else WAVES
     # the product z = x y as one level of Karatsuba (three 76 x 76-limb products, section 2K below) instead of
     # 152 x 152 operand scanning; "nokara" keeps the latter (a correct schedule, for the A/B)
     KARA = "nokara" not in DBG
@@ -199,7 +211,8 @@ def gen_addb(name: str, dbg="") -> str:
     RR = 44                                       # r dwords (reuses DQ after the subtraction) v44..v75, v76
     R128 = 76
     TT, TT128 = 80, 112                           # r - N dwords v80..v111 (+ dword 128): ZL is dead by then
-    NVGPR = 168
+    NVGPR = 206 if PAIR else 168
+    XS = 168                                      # pair: x's limbs kept across the first product
 
     def X(k):
         return f"v{XB + k}"
@@ -222,7 +235,7 @@ def gen_addb(name: str, dbg="") -> str:
     # s[28:29] live lanes, s30 = 256, s31 = 65536, s32 = 2^24, s33 = 0x80808080, s[34:35] x index list,
     # s[36:37] y index list (0: direct rows), s[38:39] carry scratch of the gathered addresses
     LIVE = "s[28:29]"
-    NSGPR = 68 if "stamp" in DBG else 50 if MFZ else 42   # s[40:41]: the product steps' carry-out sink; MFZ: s42..s48
+    NSGPR = 68 if "stamp" in DBG else 50 if MFZ or PAIR else 42   # s[40:41]: the product steps' carry-out sink; MFZ: s42..s48
 
     e('.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
     e('.amdhsa_code_object_version 5')
@@ -238,11 +251,17 @@ def gen_addb(name: str, dbg="") -> str:
     e('  s_load_dword s12, s[0:1], 0x20')
     e('  s_load_dwordx2 s[34:35], s[0:1], 0x28')
     e('  s_load_dwordx2 s[36:37], s[0:1], 0x30')
+    if PAIR:                                      # s[42:43] y2, s[44:45] out2, s[46:47] y, s[48:49] out
+        assert not MFZ and "stamp" not in DBG
+        e('  s_load_dwordx2 s[42:43], s[0:1], 0x38')
+        e('  s_load_dwordx2 s[44:45], s[0:1], 0x40')
+        e('  s_load_dwordx2 s[46:47], s[0:1], 0x8')
+        e('  s_load_dwordx2 s[48:49], s[0:1], 0x10')
     bm.lane_masks(e)
     bm.fold_consts(e)
     e('  s_waitcnt lgkmcnt(0)')
     # ---- constant image -> LDS (768 threads x 16 B = 12,288 B per pass), batch counter = 0 --------------------
-    bm.image_to_lds(e, IMG_BYTES, WAVES, LDS_CNT, 's[10:11]', 's[16:17]', V_TID, V_ROW, V_LDSI, XB, V_TMP)
+    bm.image_to_lds(e, IMG_BYTES, NW, LDS_CNT, 's[10:11]', 's[16:17]', V_TID, V_ROW, V_LDSI, XB, V_TMP)
     e('  s_waitcnt lgkmcnt(0)')
     e('  s_barrier')
     # ---- the wave's batches of 16 ciphertexts: the k-th batch the workgroup hands out is wg + k * nwg
@@ -435,11 +454,19 @@ def gen_addb(name: str, dbg="") -> str:
         e(f'  s_branch {lab}_loop')
         e(f'{lab}_done:')
 
+    body0 = len(o)
+    if PAIR:
+        e('  s_mov_b64 s[6:7], s[46:47]')
+        e('  s_mov_b64 s[8:9], s[48:49]')
     e('// @phase load')
     # ---- 1. x -> X limbs; y -> limbs -> the wave's A column (rows 38j + k of column c) ------------------
     # both rows in flight at once (one memory latency per batch), then y's limbs (via X) to the A column
     YW = MZ_YI if MFZ else WY                     # the matrix-core product keeps y's dwords at v80 (section 2M)
+    if PAIR:
+        e('// @pair x0')
     issue_row('s[4:5]', 's[34:35]', W0, GA)
+    if PAIR:
+        e('// @pair x1')
     issue_row('s[6:7]', 's[36:37]', YW, GA + 2)
     e('  s_waitcnt vmcnt(0)')
     e('  s_not_b64 exec, exec')                                          # dead lanes: zero operands
@@ -453,7 +480,14 @@ def gen_addb(name: str, dbg="") -> str:
         convert_row(WY, X)
         for k in range(Q):
             e(f'  ds_write_b32 v{V_ZR}, {X(k)} offset:{k * RB}')
+        if PAIR:
+            e('// @pair c0')
         convert_row(W0, X)
+        if PAIR:
+            for k in range(Q):
+                e(f'  v_mov_b32_e32 v{XS + k}, {X(k)}')
+        if PAIR:
+            e('// @pair c1')
         e('  s_waitcnt lgkmcnt(0)')
 
     def classic_product():
@@ -1235,6 +1269,24 @@ def gen_addb(name: str, dbg="") -> str:
     for i in range(8):
         e(f'  global_store_dwordx4 v{V_ROW}, {quad4(RR + 4 * i)}, s[8:9] offset:{16 * i}')
     e('  s_mov_b64 exec, -1')
+    if PAIR:
+        body = o[body0 + 2:]
+        defined = {m.group(1) for ln in body for m in [re.match(r'(\.L\w+):', ln)] if m}
+        e('  s_nop 1')
+        e('  s_mov_b64 s[6:7], s[42:43]')
+        e('  s_mov_b64 s[8:9], s[44:45]')
+        skip = False
+        for ln in body:
+            if ln in ('// @pair x0', '// @pair c0'):
+                skip = True
+                if ln == '// @pair c0':
+                    for k in range(Q):
+                        e(f'  v_mov_b32_e32 {X(k)}, v{XS + k}')
+            elif ln in ('// @pair x1', '// @pair c1'):
+                skip = False
+            elif not skip:
+                e(re.sub(r'\.L\w+', lambda m: m.group(0) + '_b' if m.group(0) in defined else m.group(0), ln))
+    o[:] = [ln for ln in o if not ln.startswith('// @pair')]
     e('// @phase loop')
     e('  s_branch .Lbatch')
     e('.Lend:')
@@ -1246,7 +1298,8 @@ def gen_addb(name: str, dbg="") -> str:
     e('')
     if "stamp" in DBG:
         o = stamp_pass(o)
-    return "\n".join(o) + "\n" + _descriptor(name, LDS_BYTES, NVGPR, NSGPR, max_wg=64 * WAVES, kargs=KARGS)
+    return "\n".join(o) + "\n" + _descriptor(name, LDS_BYTES, NVGPR, NSGPR, max_wg=64 * NW,
+                                             kargs=PAIR_KARGS if PAIR else KARGS)
 
 
 STAMP_PHASES = ['entry', 'load', 'product', 'window', 'q1stage', 'prod1', 'norm', 'q3stage', 'prod2', 'sub',

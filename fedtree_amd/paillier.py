@@ -113,6 +113,8 @@ def packed_bits_after(op, bits_a, bits_b=None, k=None):
     """Upper bound on the bits of a packed plaintext after an operation (the growth rule):
       "add": a + b                           -> max(bits_a, bits_b) + 1
       "sub": a - b = a + b (2^192 - 1)       -> max(bits_a, bits_b + 192) + 1
+      "sub_inv": a - b + 2^bits_b by b's inverse (Paillier.sub_inv_batch)
+                                             -> max(bits_a, bits_b) + 1
       "sum": k addends of at most bits_a bits (segment products, histogram bins, prefix scans)
                                              -> bits_a + ceil(log2 k)
     A fresh packed plaintext has 192 bits (a negative code fills the top field).  A result decrypts
@@ -121,6 +123,8 @@ def packed_bits_after(op, bits_a, bits_b=None, k=None):
         return max(int(bits_a), int(bits_b)) + 1
     if op == "sub":
         return max(int(bits_a), int(bits_b) + GH_PACKED_BITS) + 1
+    if op == "sub_inv":
+        return max(int(bits_a), int(bits_b)) + 1
     if op == "sum":
         return int(bits_a) + max(0, int(k) - 1).bit_length()
     raise ValueError(f"packed_bits_after: unknown op {op!r}")
@@ -612,6 +616,39 @@ class Paillier:
                    "sub_bits")
         return out
 
+    def _offset_words(self, offset, what):
+        """A public plaintext offset -> (pointer, words) of the C ABI; None or 0: no offset."""
+        if not offset:
+            return None, None, 0
+        offset = int(offset)
+        if offset < 0 or offset.bit_length() > 32 * self.n_words:
+            raise ValueError(f"{what}: offset must lie in [0, 2^{32 * self.n_words})")
+        nw = (offset.bit_length() + 31) // 32           # the fewest words that hold it
+        w = _words(offset, nw)
+        return w, _ptr(w), nw
+
+    def invert_batch(self, x):
+        """x^-1 mod n^2 (fthe_invert): Enc(-m mod n), by one modular inverse for the whole batch.  A row that
+        is no unit mod n^2 fails the call (FtheError, FTHE_ERR_ARG)."""
+        x = np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, self._cw())
+        out = np.zeros_like(x)
+        _lib.check(self.lib.fthe_invert(self._key, self.dev.ctx, _ptr(x), len(x), _ptr(out)), "invert")
+        return out
+
+    def sub_inv_batch(self, a, b, offset=None):
+        """a * b^-1 * (1 + offset n) mod n^2 (fthe_sub_inv): the plaintext m_a - m_b + offset mod n, with no
+        residue of b left in it.  offset: a non-negative Python integer that keeps the result non-negative
+        (packed pairs: 2^bits_b).  A row of b that is no unit mod n^2 fails the call with `out` unwritten."""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, self._cw())
+        b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, self._cw())
+        if b.shape != a.shape:
+            raise ValueError(f"sub_inv_batch: operand shapes differ ({a.shape} vs {b.shape})")
+        _keep, off, ow = self._offset_words(offset, "sub_inv_batch")
+        out = np.zeros_like(a)
+        _lib.check(self.lib.fthe_sub_inv(self._key, self.dev.ctx, _ptr(a), _ptr(b), len(a), off, ow, _ptr(out)),
+                   "sub_inv")
+        return out
+
     def direct_y(self, seed, index0, count):
         """(y_p, y_q) words ((count, pq_words) uint32 each) that encrypt_u64[_dev](r=None, seed=seed)
         draws for ciphertexts [index0, index0 + count) on the key holder's direct-y path
@@ -796,6 +833,24 @@ class Paillier:
         _lib.check(self.lib.fthe_sub_bits_dev(self._key, self.dev.ctx, ctypes.c_void_p(a.data_ptr()),
                                               ctypes.c_void_p(b.data_ptr()), cnt, int(bits),
                                               ctypes.c_void_p(out.data_ptr())), "sub_bits_dev")
+        return out
+
+    @_stream_ordered
+    def invert_dev(self, x, out):
+        """fthe_invert_dev on device rows; out may be x.  Synchronises the context stream once per chunk."""
+        cnt = x.numel() // self._cw()
+        _lib.check(self.lib.fthe_invert_dev(self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()), cnt,
+                                            ctypes.c_void_p(out.data_ptr())), "invert_dev")
+        return out
+
+    @_stream_ordered
+    def sub_inv_dev(self, a, b, out, offset=None):
+        """fthe_sub_inv_dev on device rows; out may be a or b.  offset as sub_inv_batch."""
+        cnt = a.numel() // self._cw()
+        _keep, off, ow = self._offset_words(offset, "sub_inv_dev")
+        _lib.check(self.lib.fthe_sub_inv_dev(self._key, self.dev.ctx, ctypes.c_void_p(a.data_ptr()),
+                                             ctypes.c_void_p(b.data_ptr()), cnt, off, ow,
+                                             ctypes.c_void_p(out.data_ptr())), "sub_inv_dev")
         return out
 
     @_stream_ordered
@@ -1020,8 +1075,8 @@ class GHPairs:
     slot_bits > 0 (include/fthe.h FTHE_GH_SLOT_*): a packed batch whose len(self) bins lie `slots` to a
     ciphertext in slots of slot_bits bits, in plane order -- g_enc holds ceil(len / slots) rows, from
     homo_encrypt(slot_bits=...) or compress().  pt_bits then bounds every slot's content and must stay
-    within slot_bits: such batches add (and merge by reduce_kway) but do not subtract or enter the
-    histogram methods; subtract first, compress after."""
+    within slot_bits: such batches add (and merge by reduce_kway) and subtract by sub_inv, but `-` and the
+    histogram methods refuse them: subtract first, compress after, or subtract with sub_inv."""
 
     def __init__(self, g, h=None, paillier=None, packed=False):
         self.g = np.ascontiguousarray(g, dtype=np.float32).copy()
@@ -1209,6 +1264,40 @@ class GHPairs:
         res.g_enc, res.h_enc = both[:len(rhs)], both[len(rhs):]
         res.encrypted = True
         return res
+
+    def sub_inv(self, rhs):
+        """self - rhs on packed batches by rhs's modular inverse (Paillier.sub_inv_batch; opt-in, `-` is
+        unchanged): the plaintext is T_a - T_b + 2^bits_b, bits_b = rhs.pt_bits, which lies in
+        [0, 2^(max(bits_a, bits_b) + 1)) and equals T_a - T_b mod 2^192, so it decodes as `-` does while
+        pt_bits grows by one bit instead of 192.  Slot-packed batches of one layout subtract slot by slot
+        (the offset in every slot); ValueError, before any device work, when the bound passes slot_bits.
+        An unencrypted side is handled as `-` handles it.  Two-ciphertext batches raise ValueError: nobody
+        tracks their plaintext bits."""
+        if not self.encrypted and not rhs.encrypted:
+            return GHPairs(self.g - rhs.g, self.h - rhs.h)
+        if not self._mode_with(rhs):
+            raise ValueError("GHPairs.sub_inv: needs packed batches (two-ciphertext plaintexts have no tracked "
+                             "bound; fthe_sub_inv with offset 2^128 subtracts them through the C ABI)")
+        if not rhs.encrypted:
+            neg = GHPairs(-rhs.g, -rhs.h)
+            return self + neg._enc_side(self.paillier, True)
+        pl = rhs.paillier if not self.encrypted else self.paillier
+        if self.slot_bits or rhs.slot_bits:
+            if not (self.encrypted and self.slot_bits and rhs.slot_bits):
+                raise ValueError("GHPairs.sub_inv: a slot-packed batch subtracts only from an encrypted "
+                                 "slot-packed batch")
+            if (len(self), self.slot_bits, self.slots) != (len(rhs), rhs.slot_bits, rhs.slots):
+                raise ValueError("GHPairs.sub_inv: slot-packed operands differ in length, slot_bits or slots")
+            bits = packed_bits_after("sub_inv", self.pt_bits, rhs.pt_bits)
+            if bits > self.slot_bits:
+                raise ValueError(f"GHPairs.sub_inv: the difference may reach {bits} bits, above the slots' "
+                                 f"{self.slot_bits}")
+            offset = sum(1 << (j * self.slot_bits + rhs.pt_bits) for j in range(self.slots))
+            return self._packed_result(pl, pl.sub_inv_batch(self.g_enc, rhs.g_enc, offset), bits, len(self),
+                                       self.slot_bits, self.slots)
+        lhs = self if self.encrypted else self._enc_side(pl, True)
+        return self._packed_result(pl, pl.sub_inv_batch(lhs.g_enc, rhs.g_enc, 1 << rhs.pt_bits),
+                                   packed_bits_after("sub_inv", lhs.pt_bits, rhs.pt_bits))
 
 
 def histogram_segments(bin_ids, cut_col_ptr, max_num_bin):

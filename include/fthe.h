@@ -492,6 +492,42 @@ int fthe_sub_bits_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uin
 int fthe_sub_bits(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
                   int bits, uint32_t *out);
 
+/* ---- negate and subtract by one batched modular inverse (opt-in; not in the reference) ----
+ * fthe_invert    out[i] = x[i]^-1 mod n^2: Enc(-m mod n), what a Paillier user means by "negate".
+ * fthe_sub_inv   out[i] = a[i] * b[i]^-1 * (1 + offset n) mod n^2: the plaintext m_a - m_b + offset (mod n).
+ *                offset: offset_words little-endian words (0 .. n_words; more: FTHE_ERR_ARG), NULL or 0
+ *                words = no offset; host memory in both forms.  It is a public constant that keeps the plaintext non-negative, so the
+ *                existing decoders read the result as it is: 2^bits_b for pair-packed plaintexts T_b <
+ *                2^bits_b (the result T_a - T_b + 2^bits_b lies in [0, 2^(max(bits a, bits b) + 1)) and
+ *                equals T_a - T_b mod 2^W), the same in every slot for slot-packed ones, 2^128 for the
+ *                two-ciphertext codes.  Unlike fthe_sub_bits it leaves no residue m_b 2^W: the growth rule is
+ *                bits(a - b) <= max(bits a, bits b) + 1, and slot-packed ciphertexts of one layout subtract.
+ * The whole batch costs one modular inverse on the host (Montgomery's trick: a tree of pairwise products on
+ * the device, the inverse of its top by GMP, the tree walked back down): about 3 products mod n^2 per row
+ * for fthe_invert and 4 for fthe_sub_inv, against fthe_sub_bits' bits + 9.
+ *   - Rows are canonical (< n^2) and so is the result: the unique integer, whatever the tree's shape.
+ *   - Alias-safe: out may be exactly x, a or b.
+ *   - Any key with the public form may call them; no private key is needed.
+ *   - Every row of x / b must be a unit mod n^2 (gcd(row, n) = 1; every ciphertext an honest party makes
+ *     is one).  One row that is not -- 0, a multiple of p or q -- fails its whole batch with FTHE_ERR_ARG
+ *     before anything is written to out (all chunks are checked before any is finished; a call of several
+ *     chunks therefore runs its product tree twice, 5 products per row).  fthe_sub_bits takes any rows.
+ *     The integer 1 (an empty histogram bin) is a unit and inverts to 1.
+ *   - The _dev forms synchronise the context stream once per chunk, for the host inversion (as
+ *     fthe_ct_to_decimal_dev does for its size).  A chunk is 2^20 rows (FTHE_INV_CHUNK overrides, read once;
+ *     at most 2^22), fewer when fthe_ctx_set_mem_limit does not admit the workspace of two rows per row.
+ *     At a 2048-bit n the down-sweep's pairs run on fthe_addb_pair, one launch for both children;
+ *     FTHE_INV_NO_PAIR=1 (read per call) puts two adds in its place, bit-identical.
+ *   - count == 0: FTHE_OK.  The host forms stage their rows through the context's device buffers.
+ *   - fthe_last_kernel_ms / fthe_last_montmuls account for the call (the host inversion's wait included);
+ *     after a call that failed (a non-unit row, FTHE_ERR_NOMEM) they still describe the call before it. */
+int fthe_invert_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t count, uint32_t *out);
+int fthe_invert(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t count, uint32_t *out);
+int fthe_sub_inv_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
+                     const uint32_t *offset, int offset_words, uint32_t *out);
+int fthe_sub_inv(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
+                 const uint32_t *offset, int offset_words, uint32_t *out);
+
 /* ---- slot-packed pairs: several (g, h) bins in one ciphertext (opt-in; not in the reference) ----
  * A pair-packed ciphertext (above) uses W = 192 plaintext bits of a key's thousands.  A slot-packed
  * one holds `slots` such plaintexts T_j, each in a slot of slot_bits bits:
@@ -520,7 +556,8 @@ int fthe_sub_bits(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_
  *                      out[i] = prod_j x[j*rows + i]^(2^(j*slot_bits)) mod n^2 (Horner: about
  *                      slot_bits + 2 products mod n^2 per slot above the lowest).  x rows canonical
  *                      (< n^2); out may alias no input.  Add and fthe_reduce_kway work on slot-packed
- *                      ciphertexts of one layout as they are; subtraction does not. */
+ *                      ciphertexts of one layout as they are; fthe_sub and fthe_sub_bits do not, fthe_sub_inv
+ *                      (with its offset in every slot) does. */
 #define FTHE_GH_SLOT_BITS_MIN 224
 int fthe_gh_slots(const fthe_key *key, int slot_bits, int short_pt);
 int fthe_pack_gh_slots_dev(fthe_ctx *ctx, const float *g, const float *h, size_t count, int slot_bits,
