@@ -132,6 +132,11 @@ _PROTOS = {
     "fthe_invert": (_I, [_P, _P, _P, _SZ, _P]),
     "fthe_sub_inv_dev": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _P]),
     "fthe_sub_inv": (_I, [_P, _P, _P, _P, _SZ, _P, _I, _P]),
+    "fthe_scalar_mul_rows_dev": (_I, [_P, _P, _P, _P, _I, _SZ, _P]),
+    "fthe_scalar_mul_rows": (_I, [_P, _P, _P, _P, _I, _SZ, _P]),
+    "fthe_dot_segments_dev": (_I, [_P, _P, _P, _SZ, _P, _I, _P, _P, _SZ, _P]),
+    "fthe_dot_segments": (_I, [_P, _P, _P, _SZ, _P, _I, _P, _P, _SZ, _P]),
+    "fthe_debug_dot_plan": (_I, [_I, _SZ, _SZ, _P]),
     "fthe_gh_slots": (_I, [_P, _I, _I]),
     "fthe_pack_gh_slots_dev": (_I, [_P, _P, _P, _SZ, _I, _I, _P]),
     "fthe_unpack_gh_slots_dev": (_I, [_P, _P, _I, _SZ, _I, _I, _P, _P, _P, _P]),

@@ -300,9 +300,13 @@ struct fthe_ctx {
     DevBuf gh[3];                           // packed / slot-packed pairs: plaintext words of an encrypt, one decrypt
                                             // chunk's plaintext words, the host forms' floats / codes
     PinBuf inv_top;                         // batched inverse: every chunk's top rows, to the host and back
+    DevBuf dw[20];                         // per-row weights (fthe_scalar_mul_rows / fthe_dot_segments): kDw* below
     void *cub_tmp = nullptr; size_t cub_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double last_mm = 0;
+    // a call made of several inner calls (CallSpan): they leave ev0 alone and add their products to span_mm
+    bool span = false;
+    double span_mm = 0;
     bool timed = false;
     // optional per-launch timing of the montprog kernel (bench roofline)
     bool prof = false;
@@ -1736,6 +1740,12 @@ static void fill_dec_consts(Launch &R, int halves, bool s80 = false) {
     R.fill(SL_T5, s80 ? k->cl_one : k->c_one);
 }
 
+// The start of what fthe_last_kernel_ms times; inside a CallSpan the span's own start stands.
+static int mark_start(fthe_ctx *c) {
+    if (!c->span) HIPOK(hipEventRecord(c->ev0, c->stream));
+    return FTHE_OK;
+}
+
 int begin_call(fthe_ctx *c, const fthe_key *k, size_t count, Launch &Lc, int nslots, Shape sh,
                size_t chunk = 0) {
     if (!c || !k) return FTHE_ERR_ARG;
@@ -1755,17 +1765,41 @@ int begin_call(fthe_ctx *c, const fthe_key *k, size_t count, Launch &Lc, int nsl
     int rc = c->slots.ensure(need);
     Lc.base = c->slots.p;
     if (rc) return rc;
-    HIPOK(hipEventRecord(c->ev0, c->stream));
-    return FTHE_OK;
+    return mark_start(c);
 }
 
 int end_call(fthe_ctx *c, Launch &Lc) {
+    if (c->span) {                          // an inner call: its products join the whole call's
+        c->span_mm += Lc.mm;
+        Lc.mm = 0;
+        return hipGetLastError() != hipSuccess ? FTHE_ERR_HIP : FTHE_OK;
+    }
     HIPOK(hipEventRecord(c->ev1, c->stream));
     c->timed = true;
     c->last_mm = Lc.mm;
     if (hipGetLastError() != hipSuccess) return FTHE_ERR_HIP;
     return FTHE_OK;
 }
+
+// A call composed of inner calls (the per-row powers, the dot product): fthe_last_kernel_ms and
+// fthe_last_montmuls then cover all of them, from the span's start to its finish.  Nests (the inner span is idle).
+struct CallSpan {
+    fthe_ctx *c; bool outer;
+    explicit CallSpan(fthe_ctx *c_) : c(c_), outer(!c_->span) {
+        if (!outer) return;
+        (void)hipEventRecord(c->ev0, c->stream);
+        c->span = true; c->span_mm = 0;
+    }
+    ~CallSpan() { if (outer) c->span = false; }
+    int finish() {
+        if (!outer) return FTHE_OK;
+        c->span = false;
+        HIPOK(hipEventRecord(c->ev1, c->stream));
+        c->timed = true;
+        c->last_mm = c->span_mm;
+        return hipGetLastError() != hipSuccess ? FTHE_ERR_HIP : FTHE_OK;
+    }
+};
 
 // The form of a CRT decrypt or of an encrypt, and the memory of every region it runs in.
 //   quad:  at most dec_quad_max() rows of a key with the s80 shape: both halves on the four-lane kernel, each
@@ -3458,21 +3492,18 @@ extern "C" int fthe_decrypt_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_
 // the last is followed by a product by R^2.  Rows whose top planes run past count (the last rows) start one
 // plane lower instead of multiplying by 1: two programs, for rows [0, nA) with J planes and [nA, rows) with
 // J - 1, uploaded together.  Row I/O where the key has it and the planes fit the row table, else the slot form.
-extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, int slot_bits,
-                                          uint32_t *out, int slots) {
-    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
-    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
-    if (rc) return rc;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
-    if (!count) return FTHE_OK;
-    const size_t rows = (count + slots - 1) / slots, cw = 2 * (size_t)k->n_words;
-    const int J = (int)((count + rows - 1) / rows);          // planes of the first nA rows; J - 1 for the rest
-    const size_t nA = count - (size_t)(J - 1) * rows;
+//
+// horner_planes is that body for any number of squarings per plane: out[i] = prod_j x[j rows + i]^(2^(j sq)), rows
+// [0, nA) with J planes and [nA, rows) with J - 1.  The dot product's windows (fthe_dot_segments) are its other
+// caller; there out may be plane 0's rows (every row is read before it is written, lane by lane or through slots).
+static int horner_planes(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t rows, int J, size_t nA, int sq,
+                         uint32_t *out) {
+    const size_t cw = 2 * (size_t)k->n_words;
     const bool rowio = k->rowio && J + 1 <= 16;
     const int base = nslots_for(k);
     Launch Lc;
-    rc = rowio ? begin_call(c, k, rows, Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
-               : begin_call(c, k, rows, Lc, base + J, k->sn2);
+    int rc = rowio ? begin_call(c, k, rows, Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
+                   : begin_call(c, k, rows, Lc, base + J, k->sn2);
     if (rc) return rc;
     const int S = Lc.S, L = Lc.L;
     auto horner = [&](int planes) {
@@ -3481,7 +3512,7 @@ extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32
         if (rowio) p.loadw(planes - 1); else p.loadx(base + planes - 1);
         for (int j = planes - 2; j >= 0; j--) {
             p.mul(SL_C0);                                     // into Montgomery form
-            if (rowio) { p.sqr(slot_bits); p.mulw(j); } else p.sqr_mul(slot_bits, base + j);
+            if (rowio) { p.sqr(sq); p.mulw(j); } else p.sqr_mul(sq, base + j);
         }
         if (rowio) p.storew(planes); else p.storex(SL_OUTP);
         p.end();
@@ -3491,7 +3522,7 @@ extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32
     Prog both; both.w = pa.w; both.w.insert(both.w.end(), pb.w.begin(), pb.w.end());
     fthe_key::PH ph;
     if ((rc = upload_dyn_prog(c, both, ph, c->io[3]))) return rc;
-    HIPOK(hipEventRecord(c->ev0, c->stream));
+    if ((rc = mark_start(c))) return rc;
     Lc.fill(SL_C0, k->c_R2n2);
     // rows [r0, r1) of the output, each the Horner form of its `planes` planes
     auto run = [&](size_t r0, size_t r1, int planes, const Prog &p, const uint32_t *dprog) -> int {
@@ -3518,6 +3549,19 @@ extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32
     if ((rc = run(0, nA, J, pa, dprog))) return rc;
     if (J > 1 && (rc = run(nA, rows, J - 1, pb, dprog + pa.w.size()))) return rc;
     return end_call(c, Lc);
+}
+
+extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count, int slot_bits,
+                                          uint32_t *out, int slots) {
+    if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
+    if (rc) return rc;
+    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!count) return FTHE_OK;
+    const size_t rows = (count + slots - 1) / slots;
+    const int J = (int)((count + rows - 1) / rows);          // planes of the first nA rows; J - 1 for the rest
+    const size_t nA = count - (size_t)(J - 1) * rows;
+    return horner_planes(k, c, x, rows, J, nA, slot_bits, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -4153,7 +4197,7 @@ struct GatherProd {
         Prog blob; blob.w = p.w; blob.w.insert(blob.w.end(), rl.begin(), rl.end());
         fthe_key::PH ph;
         if ((rc = upload_dyn_prog(c, blob, ph, c->io[3]))) return rc;
-        HIPOK(hipEventRecord(c->ev0, c->stream));
+        if ((rc = mark_start(c))) return rc;
         hipLaunchKernelGGL(k_fill_const, Lc.grid(), dim3(256), 0, c->stream,
                            (const uint32_t *)c->io[3].p + prog_words, Lc.slot(SL_C0), Lc.S, Lc.L);
         return FTHE_OK;
@@ -4558,6 +4602,344 @@ extern "C" int fthe_scalar_mul_words_dev(fthe_key *k, fthe_ctx *c, const uint32_
 }
 
 // ---------------------------------------------------------------------------
+// Per-row plaintext weights: fthe_scalar_mul_rows_dev / fthe_dot_segments_dev.
+// Both are built from products of row ranges (the add of the key: fthe_addb_q152 with gathered operands at a
+// 2048-bit n, else the add program on rows gathered into a buffer first), the segmented product and the Horner
+// programs; what is new on the device is the control (fthe_hist.hip: k_exp_*, k_dot_*).
+namespace {
+// c->dw: table x^1..x^15 | window gather lists | gathered operand rows | composed terms or bucket products |
+// bucket CSR counters | bucket members | digit-position lists | running product S | digit weights W | flags |
+// the host forms' exponents, seg_ptr, idx | the bucket products' pass plan, group lists, compacted lists, group
+// fates, two level buffers and the compacted products
+enum { kDwTable = 0, kDwLists, kDwTmp, kDwRows, kDwCsr, kDwIdx, kDwDigit, kDwS, kDwW, kDwFlags, kDwHostE, kDwHostSeg,
+       kDwHostIdx, kDwPlan, kDwGidx, kDwCg, kDwWhere, kDwLvlA, kDwLvlB, kDwProd, kDwCount };
+
+size_t env_size(const char *name) {           // read per call (A/B, chunk-boundary tests); 0: unset
+    const char *e = getenv(name);
+    return e ? (size_t)strtoull(e, nullptr, 10) : 0;
+}
+
+// The product-count model that picks the dot product's form (tools/dot_model.py states it; integers only, so
+// both sides agree exactly): 0 = composed (per-row powers, then the segmented product), else the window width.
+// Measured constants: a product of the bucket form costs 3/2 of one of the composed form (gathered
+// operands, Horner on the program kernel), and each of the 2 (D - 1) launches of the digit-weight loop costs what
+// kDotLaunch products do however few rows it covers.  Costs are in half products.
+constexpr uint64_t kDotLaunch = 32768;
+uint64_t rows_products(int bits) { return bits > 0 ? 14 + 5 * (uint64_t)((bits + 3) / 4 - 1) : 0; }
+uint64_t dot_cost(int bits, uint64_t terms, uint64_t nseg, int w) {
+    if (!w) return 2 * (terms * rows_products(bits) + terms + terms / 7 + nseg);
+    const uint64_t nwin = (uint64_t)((bits + w - 1) / w), D = ((uint64_t)1 << w) - 1, entries = terms * nwin;
+    return 3 * (entries + entries / 7 + nseg * (nwin * 2 * (D - 1) + (nwin - 1) * (uint64_t)(w + 2))) +
+           2 * 2 * (D - 1) * kDotLaunch;
+}
+int dot_plan(int bits, uint64_t terms, uint64_t nseg) {
+    if (bits <= 0 || !terms) return 0;
+    int best = 0;
+    uint64_t best_cost = dot_cost(bits, terms, nseg, 0);
+    for (int w : {4, 8}) {
+        const uint64_t cost = dot_cost(bits, terms, nseg, w);
+        if (cost < best_cost) { best_cost = cost; best = w; }
+    }
+    return best;
+}
+
+// Products of row ranges mod n^2 on the key's add, accounted like it.  Begun anew after any inner call (those
+// may regrow the slot region).
+struct RowOps {
+    InvTree T{nullptr, nullptr};
+    int begin(fthe_key *k, fthe_ctx *c, size_t maxrows) {
+        T.k = k; T.c = c; T.cw = 2 * (size_t)k->n_words;
+        int rc = k->rowio ? begin_call(c, k, addb() ? 1 : maxrows, T.Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
+                          : begin_call(c, k, maxrows, T.Lc, nslots_for(k), k->sn2);
+        if (rc) return rc;
+        if (!addb() && (!k->rowio || !k->add_classical)) T.Lc.fill(SL_C0, k->c_R2n2);
+        return FTHE_OK;
+    }
+    bool addb() const { return T.k->d_addb && T.c->fn_addb; }
+    // out = x y over cnt contiguous rows; out may be exactly x or y, and x may be y (a batch of rows is read
+    // whole before it is written: gen_addb.py loads in its step 1 and stores in step 8; the programs work lane by lane)
+    int mul(const uint32_t *x, const uint32_t *y, uint32_t *out, size_t cnt) { return T.mul(x, y, out, cnt); }
+    // out[g] = src[idx[g]] (idx[g] < 0: the integer 1); no product
+    int gather(const uint32_t *src, const int64_t *idx, uint32_t *out, size_t cnt) {
+        if (cnt)
+            hipLaunchKernelGGL(k_gather_rows, grid256(cnt * T.cw), dim3(256), 0, T.c->stream, src, idx, (int)T.cw, cnt, out);
+        return FTHE_OK;
+    }
+    // out = x src[yi] over cnt rows (x contiguous; out may be exactly x; src is another buffer)
+    int gmul(const uint32_t *x, const uint32_t *src, const int64_t *yi, uint32_t *out, size_t cnt) {
+        if (!cnt) return FTHE_OK;
+        if (addb()) {
+            T.Lc.mm += (double)cnt;
+            return launch_addb(T.c, T.k, x, src, out, cnt, nullptr, yi);
+        }
+        DevBuf &tmp = T.c->dw[kDwTmp];
+        if (int rc = tmp.ensure(cnt * T.cw * 4)) return rc;
+        if (int rc = gather(src, yi, (uint32_t *)tmp.p, cnt)) return rc;
+        return T.mul(x, (const uint32_t *)tmp.p, out, cnt);
+    }
+    // out = src[xi] src[yi] over cnt rows; out is another buffer
+    int gmul2(const uint32_t *src, const int64_t *xi, const int64_t *yi, uint32_t *out, size_t cnt) {
+        if (!cnt) return FTHE_OK;
+        if (addb()) {
+            T.Lc.mm += (double)cnt;
+            return launch_addb(T.c, T.k, src, src, out, cnt, xi, yi);
+        }
+        if (int rc = gather(src, xi, out, cnt)) return rc;
+        return gmul(out, src, yi, out, cnt);
+    }
+    int end() { return end_call(T.c, T.Lc); }
+};
+static_assert(kDwCount <= 20, "fthe_ctx::dw");
+
+int rows_one(fthe_ctx *c, const fthe_key *k, uint32_t *out, size_t count) {
+    const size_t cw = 2 * (size_t)k->n_words;
+    if (count) hipLaunchKernelGGL(k_rows_one, grid256(count * cw), dim3(256), 0, c->stream, (int)cw, count, out);
+    return FTHE_OK;
+}
+
+// *bits = bit length of the largest of the count exponents; FTHE_ERR_ARG when an index (nullable list of count
+// entries) lies outside [0, x_rows).  One read-back.
+int weights_scan(fthe_ctx *c, const uint32_t *e, int ew, size_t count, const int64_t *idx, size_t x_rows, int *bits) {
+    if (int rc = c->dw[kDwFlags].ensure(64)) return rc;
+    int *f = (int *)c->dw[kDwFlags].p;
+    HIPOK(hipMemsetAsync(f, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_exp_maxbits, grid256(count), dim3(256), 0, c->stream, e, ew, count, f);
+    if (idx) hipLaunchKernelGGL(k_idx_check, grid256(count), dim3(256), 0, c->stream, idx, count, x_rows, f + 1);
+    int h[2] = {0, 0};
+    HIPOK(hipMemcpyAsync(h, f, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    if (h[1]) return FTHE_ERR_ARG;
+    *bits = h[0];
+    return FTHE_OK;
+}
+
+// out[i] = x[i]^e[i] by fixed 4-bit windows, chunk by chunk: the table T_d = x^d (d = 1 .. 15, 14 products), the
+// gather lists g_j of every window, then acc = T[g_top] and per lower window four squarings and acc T[g_j]:
+// 14 + 5 (nwin - 1) products per row, nwin = ceil(bits / 4) for the call's largest exponent (windows above it are
+// never run; bits = 0 writes ones).  bits < 0: reduced here.  out may be exactly x (the chunk's x goes into the
+// table before its out rows are written).
+int rows_impl(fthe_key *k, fthe_ctx *c, const uint32_t *x, const uint32_t *e, int e_words, size_t count,
+              uint32_t *out, int bits) {
+    CallSpan span(c);
+    int rc;
+    if (bits < 0 && (rc = weights_scan(c, e, e_words, count, nullptr, 0, &bits))) return rc;
+    if (bits == 0) {
+        if ((rc = rows_one(c, k, out, count))) return rc;
+        return span.finish();
+    }
+    const int nwin = (bits + 3) / 4;
+    const size_t cw = 2 * (size_t)k->n_words, row = cw * 4;
+    size_t chunk = env_size("FTHE_ROWS_CHUNK");
+    if (!chunk) chunk = (size_t)1 << 17;
+    chunk = std::min(chunk, count);
+    if (c->mem_limit && 15 * chunk * row > c->mem_limit && 15 * chunk * row > c->dw[kDwTable].n) {
+        chunk = c->mem_limit / (15 * row);
+        if (!chunk) return FTHE_ERR_NOMEM;
+    }
+    if ((rc = c->dw[kDwTable].ensure(15 * chunk * row)) || (rc = c->dw[kDwLists].ensure((size_t)nwin * chunk * 8)))
+        return rc;
+    uint32_t *tab = (uint32_t *)c->dw[kDwTable].p;
+    int64_t *g = (int64_t *)c->dw[kDwLists].p;
+    RowOps ops;
+    if ((rc = ops.begin(k, c, chunk))) return rc;
+    for (size_t off = 0; off < count; off += chunk) {
+        const size_t m = std::min(chunk, count - off);
+        uint32_t *acc = out + off * cw;
+        hipLaunchKernelGGL(k_exp_windows, grid256(m), dim3(256), 0, c->stream, e + off * (size_t)e_words, e_words, m,
+                           nwin, g);
+        HIPOK(hipMemcpyAsync(tab, x + off * cw, m * row, hipMemcpyDeviceToDevice, c->stream));
+        for (int d = 2; d <= 15; d++)
+            if ((rc = ops.mul(tab + (size_t)(d - 2) * m * cw, tab, tab + (size_t)(d - 1) * m * cw, m))) return rc;
+        if ((rc = ops.gather(tab, g + (size_t)(nwin - 1) * m, acc, m))) return rc;
+        for (int j = nwin - 2; j >= 0; j--) {
+            for (int s = 0; s < 4; s++)
+                if ((rc = ops.mul(acc, acc, acc, m))) return rc;
+            if ((rc = ops.gmul(acc, tab, g + (size_t)j * m, acc, m))) return rc;
+        }
+    }
+    if ((rc = ops.end())) return rc;
+    return span.finish();
+}
+
+// Bucket products: R[b] = prod of x[bidx[t]] over t in [bptr[b], bptr[b + 1]) (1 for an empty bucket).  The passes of
+// the segmented product (groups of up to K members until one group per bucket is left), but most buckets hold
+// no member or one, and a group of fewer than two members needs no product: each pass compacts the groups that do
+// (k_dot_active), multiplies those alone -- K - 1 products a group -- and a gather puts every group's row in place.
+// Two 8-byte read-backs per pass.
+int dot_bucket_rows(fthe_key *k, fthe_ctx *c, const uint32_t *x, const int64_t *bptr, const int64_t *bidx, size_t nb,
+                    int64_t total, uint32_t *R) {
+    const int K = GatherProd::K;
+    const size_t cw = 2 * (size_t)k->n_words, row = cw * 4;
+    const size_t maxg = (size_t)total / K + nb, maxa = std::min(maxg, (size_t)total / 2 + 1);
+    hipStream_t st = c->stream;
+    int rc;
+    // kDwPlan: groups per bucket (nb + 1) | group starts, two generations (nb + 1 each) | the active-group counter
+    if ((rc = c->dw[kDwPlan].ensure((3 * (nb + 1) + 1) * 8)) || (rc = c->dw[kDwGidx].ensure((size_t)K * maxg * 8)) ||
+        (rc = c->dw[kDwCg].ensure((size_t)K * maxg * 8)) || (rc = c->dw[kDwWhere].ensure(maxg * 8)) ||
+        (rc = c->dw[kDwLvlA].ensure(maxg * row)) || (rc = c->dw[kDwLvlB].ensure(maxg * row)) ||
+        (rc = c->dw[kDwProd].ensure(maxa * row))) return rc;
+    int64_t *ng = (int64_t *)c->dw[kDwPlan].p, *gp[2] = {ng + nb + 1, ng + 2 * (nb + 1)};
+    unsigned long long *nact = (unsigned long long *)(ng + 3 * (nb + 1));
+    int64_t *gidx = (int64_t *)c->dw[kDwGidx].p, *cg = (int64_t *)c->dw[kDwCg].p, *where = (int64_t *)c->dw[kDwWhere].p;
+    uint32_t *lvl[2] = {(uint32_t *)c->dw[kDwLvlA].p, (uint32_t *)c->dw[kDwLvlB].p}, *prod = (uint32_t *)c->dw[kDwProd].p;
+    RowOps ops;
+    if ((rc = ops.begin(k, c, maxa))) return rc;
+    const int64_t *seg = bptr, *members = bidx;
+    const uint32_t *src = x;
+    for (int pass = 0;; pass++) {
+        int64_t *gptr = gp[pass & 1];
+        hipLaunchKernelGGL(k_group_counts, grid256(nb + 1), dim3(256), 0, st, seg, nb, K, ng);
+        if ((rc = exclusive_scan_i64(ng, gptr, nb + 1, c->cub_tmp, c->cub_bytes, st))) return rc;
+        int64_t G = 0;
+        HIPOK(hipMemcpyAsync(&G, gptr + nb, 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        if (G < (int64_t)nb || (size_t)G > maxg) return FTHE_ERR_ARG;
+        hipLaunchKernelGGL(k_plan_groups, grid256((size_t)G), dim3(256), 0, st, seg, members, nb, gptr, (size_t)G, K, gidx);
+        HIPOK(hipMemsetAsync(nact, 0, 8, st));
+        hipLaunchKernelGGL(k_dot_active, grid256((size_t)G), dim3(256), 0, st, gidx, (size_t)G, K, nact, cg, where);
+        unsigned long long A = 0;
+        HIPOK(hipMemcpyAsync(&A, nact, 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        if (A > maxa) return FTHE_ERR_ARG;
+        if ((rc = ops.gmul2(src, cg, cg + (size_t)G, prod, (size_t)A))) return rc;
+        for (int j = 2; j < K; j++)
+            if ((rc = ops.gmul(prod, src, cg + (size_t)j * G, prod, (size_t)A))) return rc;
+        const bool last = (size_t)G == nb;
+        uint32_t *dst = last ? R : lvl[pass & 1];
+        hipLaunchKernelGGL(k_gather_rows2, grid256((size_t)G * cw), dim3(256), 0, st, src, prod, where, (int)cw, (size_t)G,
+                           dst);
+        if (last) break;
+        seg = gptr; members = nullptr; src = dst;
+    }
+    return ops.end();
+}
+
+// The bucket form for the segments [s0, s0 + ns): bucket CSR on the device, bucket products R (dot_bucket_rows),
+// digit weights W[j ns + s] = prod_d R[s][j][d]^d by a running product down the digits (S <- S R_d,
+// W <- W S: 2 (D - 1) products per (segment, window)), then Horner across the windows, w squarings per plane.
+int dot_buckets(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t x_rows, const uint32_t *e, int e_words,
+                const int64_t *seg, const int64_t *idx, size_t nseg, size_t terms, size_t s0, size_t ns, int w,
+                int nwin, uint32_t *out) {
+    const size_t cw = 2 * (size_t)k->n_words, row = cw * 4;
+    const int D = (1 << w) - 1;
+    const size_t nsj = ns * (size_t)nwin, nb = nsj * (size_t)D;
+    hipStream_t st = c->stream;
+    int rc;
+    // kDwCsr: counts (u64, nb + 1) | counts as int64 (nb + 1) | bptr (nb + 1) | cursor (u64, nb)
+    if ((rc = c->dw[kDwCsr].ensure(4 * (nb + 1) * 8)) || (rc = c->dw[kDwRows].ensure(nb * row))) return rc;
+    unsigned long long *cnt = (unsigned long long *)c->dw[kDwCsr].p;
+    int64_t *tmp = (int64_t *)(cnt + nb + 1), *bptr = tmp + nb + 1;
+    unsigned long long *cursor = (unsigned long long *)(bptr + nb + 1);
+    HIPOK(hipMemsetAsync(cnt, 0, (nb + 1) * 8, st));
+    HIPOK(hipMemsetAsync(cursor, 0, nb * 8, st));
+    hipLaunchKernelGGL(k_dot_count, grid256(terms), dim3(256), 0, st, e, e_words, seg, nseg, terms, s0, ns, w, nwin, cnt);
+    hipLaunchKernelGGL(k_u64_to_i64, grid256(nb + 1), dim3(256), 0, st, cnt, tmp, nb + 1);
+    if ((rc = exclusive_scan_i64(tmp, bptr, nb + 1, c->cub_tmp, c->cub_bytes, st))) return rc;
+    int64_t total = 0;
+    HIPOK(hipMemcpyAsync(&total, bptr + nb, 8, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    if (total < 0 || (size_t)total > terms * (size_t)nwin) return FTHE_ERR_ARG;
+    if ((rc = c->dw[kDwIdx].ensure(std::max<size_t>(1, (size_t)total) * 8))) return rc;
+    int64_t *bidx = (int64_t *)c->dw[kDwIdx].p;
+    hipLaunchKernelGGL(k_dot_scatter, grid256(terms), dim3(256), 0, st, e, e_words, seg, nseg, terms, s0, ns, w, nwin,
+                       idx, bptr, cursor, bidx);
+    uint32_t *R = (uint32_t *)c->dw[kDwRows].p;
+    if ((rc = dot_bucket_rows(k, c, x, bptr, bidx, nb, total, R))) return rc;
+    // digit weights
+    if ((rc = c->dw[kDwDigit].ensure(nb * 8)) || (rc = c->dw[kDwS].ensure(nsj * row)) ||
+        (rc = c->dw[kDwW].ensure(nsj * row))) return rc;
+    int64_t *yi = (int64_t *)c->dw[kDwDigit].p;
+    uint32_t *S = (uint32_t *)c->dw[kDwS].p, *W = (uint32_t *)c->dw[kDwW].p;
+    hipLaunchKernelGGL(k_dot_digit_lists, grid256(nb), dim3(256), 0, st, ns, nwin, D, yi);
+    RowOps ops;
+    if ((rc = ops.begin(k, c, nsj))) return rc;
+    if ((rc = ops.gather(R, yi, S, nsj))) return rc;
+    HIPOK(hipMemcpyAsync(W, S, nsj * row, hipMemcpyDeviceToDevice, st));
+    for (int i = 1; i < D; i++) {
+        if ((rc = ops.gmul(S, R, yi + (size_t)i * nsj, S, nsj))) return rc;
+        if ((rc = ops.mul(W, S, W, nsj))) return rc;
+    }
+    if ((rc = ops.end())) return rc;
+    // Horner from the top window, at most 15 planes a program (the row table's 16 entries): a piece's result
+    // takes the place of its lowest plane and is the top plane of the next piece
+    for (int hi = nwin - 1;;) {
+        const int lo = std::max(0, hi - 14);
+        uint32_t *planes = W + (size_t)lo * ns * cw;
+        if ((rc = horner_planes(k, c, planes, ns, hi - lo + 1, ns, w, lo ? planes : out + s0 * cw))) return rc;
+        if (!lo) break;
+        hi = lo;
+    }
+    return FTHE_OK;
+}
+
+int dot_impl(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t x_rows, const uint32_t *e, int e_words,
+             const int64_t *seg, const int64_t *idx, size_t nseg, int64_t total, uint32_t *out) {
+    const size_t terms = (size_t)total, cw = 2 * (size_t)k->n_words, row = cw * 4;
+    CallSpan span(c);
+    int rc, bits = 0;
+    if (terms && (rc = weights_scan(c, e, e_words, terms, idx, x_rows, &bits))) return rc;
+    if (bits == 0) {                            // no term, or every weight 0
+        if ((rc = rows_one(c, k, out, nseg))) return rc;
+        return span.finish();
+    }
+    const char *force = getenv("FTHE_DOT_WINDOW");
+    int w = force ? atoi(force) : dot_plan(bits, terms, nseg);
+    if (w != 0 && w != 4 && w != 8) w = dot_plan(bits, terms, nseg);
+    if (w == 0) {
+        // composed: the powers of the gathered terms, then the segmented product
+        if ((rc = c->dw[kDwRows].ensure(terms * row))) return rc;
+        uint32_t *G = (uint32_t *)c->dw[kDwRows].p;
+        if (idx) hipLaunchKernelGGL(k_gather_rows, grid256(terms * cw), dim3(256), 0, c->stream, x, idx, (int)cw, terms, G);
+        if ((rc = rows_impl(k, c, idx ? G : x, e, e_words, terms, G, bits))) return rc;
+        if ((rc = reduce_segments_csr(k, c, G, terms, seg, nullptr, nseg, total, out))) return rc;
+        return span.finish();
+    }
+    const int nwin = (bits + w - 1) / w;
+    const size_t per_seg = (size_t)nwin * (size_t)((1 << w) - 1) * row;
+    size_t cap = (size_t)1 << 30;
+    if (c->mem_limit && c->mem_limit < cap) cap = c->mem_limit;
+    size_t chunk = cap / per_seg;
+    if (!chunk) return FTHE_ERR_NOMEM;
+    if (const size_t forced = env_size("FTHE_DOT_SEG_CHUNK")) chunk = std::min(chunk, forced);
+    for (size_t s0 = 0; s0 < nseg; s0 += chunk)
+        if ((rc = dot_buckets(k, c, x, x_rows, e, e_words, seg, idx, nseg, terms, s0, std::min(chunk, nseg - s0), w,
+                              nwin, out))) return rc;
+    return span.finish();
+}
+}  // namespace
+
+extern "C" int fthe_debug_dot_plan(int e_bits, size_t terms, size_t nseg, int *window) {
+    if (e_bits < 0 || !window) return FTHE_ERR_ARG;
+    *window = dot_plan(e_bits, terms, nseg);
+    return FTHE_OK;
+}
+
+extern "C" int fthe_scalar_mul_rows_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, const uint32_t *e, int e_words,
+                                        size_t count, uint32_t *out) {
+    if (!k || !c || e_words < 1 || e_words > k->n_words || ((!x || !e || !out) && count)) return FTHE_ERR_ARG;
+    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (k->device != c->device) return FTHE_ERR_ARG;
+    if (!count) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    return rows_impl(k, c, x, e, e_words, count, out, -1);
+}
+
+extern "C" int fthe_dot_segments_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t x_rows, const uint32_t *e,
+                                     int e_words, const int64_t *seg_ptr, const int64_t *idx, size_t nseg,
+                                     uint32_t *out) {
+    if (!k || !c || e_words < 1 || e_words > k->n_words || !seg_ptr || (nseg && !out)) return FTHE_ERR_ARG;
+    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (k->device != c->device) return FTHE_ERR_ARG;
+    if (!nseg) return FTHE_OK;
+    HIPOK(hipSetDevice(c->device));
+    int64_t total = 0;
+    HIPOK(hipMemcpyAsync(&total, seg_ptr + nseg, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPOK(hipStreamSynchronize(c->stream));
+    if (total < 0 || (!idx && (size_t)total > x_rows) || ((!x || !e) && total)) return FTHE_ERR_ARG;
+    return dot_impl(k, c, x, x_rows, e, e_words, seg_ptr, idx, nseg, total, out);
+}
+
+// ---------------------------------------------------------------------------
 // Host-resident variants: stage through device buffers, synchronous.
 namespace {
 struct HostIO {
@@ -4958,6 +5340,46 @@ extern "C" int fthe_scalar_mul_words(fthe_key *k, fthe_ctx *c, const uint32_t *x
     return host_in_out(c, x, bytes, out, bytes, [&](const uint32_t *dx, uint32_t *dout) {
         return fthe_scalar_mul_words_dev(k, c, dx, e, e_words, count, dout);
     });
+}
+
+extern "C" int fthe_scalar_mul_rows(fthe_key *k, fthe_ctx *c, const uint32_t *x, const uint32_t *e, int e_words,
+                                    size_t count, uint32_t *out) {
+    if (!k || !c || e_words < 1 || e_words > k->n_words || ((!x || !e || !out) && count)) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t bytes = count * 2 * (size_t)k->n_words * 4;
+    HostIO io{c}; void *dx, *de, *dout; int rc;
+    if ((rc = io.in(0, x, bytes, &dx)) || (rc = io.in(1, e, count * (size_t)e_words * 4, &de)) ||
+        (rc = io.outbuf(2, bytes, &dout))) return rc;
+    if ((rc = fthe_scalar_mul_rows_dev(k, c, (const uint32_t *)dx, (const uint32_t *)de, e_words, count,
+                                       (uint32_t *)dout))) return rc;
+    return io.back(out, dout, bytes);
+}
+
+// x staged in io[0], out in io[4] (io[1] / io[2] are the segmented product's pass buffers, io[3] the program);
+// the exponents and the CSR in buffers of their own.
+extern "C" int fthe_dot_segments(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t x_rows, const uint32_t *e,
+                                 int e_words, const int64_t *seg_ptr, const int64_t *idx, size_t nseg, uint32_t *out) {
+    if (!k || !c || e_words < 1 || e_words > k->n_words || !seg_ptr || (nseg && !out)) return FTHE_ERR_ARG;
+    if (!nseg) return FTHE_OK;
+    const int64_t total = seg_ptr[nseg];
+    if (total < 0 || ((!x || !e) && total) || (!x && x_rows)) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    const size_t row = 2 * (size_t)k->n_words * 4;
+    HostIO io{c}; void *dx, *dout; int rc;
+    if ((rc = io.in(0, x, x_rows * row, &dx)) || (rc = io.outbuf(4, nseg * row, &dout))) return rc;
+    const void *src[3] = {e, seg_ptr, idx};
+    const size_t bytes[3] = {(size_t)total * (size_t)e_words * 4, (nseg + 1) * 8, idx ? (size_t)total * 8 : 0};
+    void *d[3] = {};
+    for (int i = 0; i < 3; i++) {
+        DevBuf &b = c->dw[kDwHostE + i];
+        if ((rc = b.ensure(std::max<size_t>(8, bytes[i])))) return rc;
+        if (bytes[i]) HIPOK(hipMemcpyAsync(b.p, src[i], bytes[i], hipMemcpyHostToDevice, c->stream));
+        d[i] = b.p;
+    }
+    if ((rc = fthe_dot_segments_dev(k, c, (const uint32_t *)dx, x_rows, (const uint32_t *)d[0], e_words,
+                                    (const int64_t *)d[1], idx ? (const int64_t *)d[2] : nullptr, nseg,
+                                    (uint32_t *)dout))) return rc;
+    return io.back(out, dout, nseg * row);
 }
 
 // ---------------------------------------------------------------------------

@@ -46,6 +46,22 @@ __global__ void k_plan_groups(const int64_t *seg, const int64_t *members, size_t
                               int K, int64_t *gidx);
 __global__ void k_zero_first_rows(const uint32_t *ez, const int64_t *seg, size_t nseg, int cw, uint32_t *ezm);
 __global__ void k_u64_to_i64(const unsigned long long *a, int64_t *b, size_t n);
+// per-row plaintext weights: bit length, window gather lists, the bucket CSR of the dot product
+__global__ void k_exp_maxbits(const uint32_t *e, int ew, size_t count, int *maxbits);
+__global__ void k_exp_windows(const uint32_t *e, int ew, size_t m, int nwin, int64_t *g);
+__global__ void k_gather_rows(const uint32_t *src, const int64_t *idx, int cw, size_t count, uint32_t *out);
+__global__ void k_rows_one(int cw, size_t count, uint32_t *out);
+__global__ void k_idx_check(const int64_t *idx, size_t n, size_t rows, int *bad);
+__global__ void k_dot_count(const uint32_t *e, int ew, const int64_t *seg, size_t nseg, size_t terms, size_t s0,
+                            size_t ns, int w, int nwin, unsigned long long *cnt);
+__global__ void k_dot_scatter(const uint32_t *e, int ew, const int64_t *seg, size_t nseg, size_t terms, size_t s0,
+                              size_t ns, int w, int nwin, const int64_t *idx, const int64_t *bptr,
+                              unsigned long long *cursor, int64_t *bidx);
+__global__ void k_dot_active(const int64_t *gidx, size_t G, int K, unsigned long long *count, int64_t *cg,
+                             int64_t *where);
+__global__ void k_gather_rows2(const uint32_t *src, const uint32_t *prod, const int64_t *where, int cw, size_t count,
+                               uint32_t *out);
+__global__ void k_dot_digit_lists(size_t ns, int nwin, int D, int64_t *yi);
 int exclusive_scan_i64(const int64_t *in, int64_t *out, size_t n, void *&tmp, size_t &tmp_bytes, hipStream_t st);
 // fthe_dec.hip: decimal wire strings on the device
 int dec_launch_chunks(const uint32_t *ct, int words, size_t count, int nch, uint32_t *chunks, hipStream_t st);

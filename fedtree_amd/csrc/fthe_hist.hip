@@ -110,4 +110,147 @@ __global__ void k_zero_first_rows(const uint32_t *__restrict__ ez, const int64_t
     ezm[t] = seg[s + 1] > seg[s] ? ez[t] : (uint32_t)(w == 0);
 }
 
+// ---------------------------------------------------------------------------
+// Per-row plaintext weights (fthe_scalar_mul_rows / fthe_dot_segments): the control of the
+// windowed powers and of the bucket (Pippenger) dot product.  Exponents are ew little-endian words per row;
+// a window of w = 4 or 8 bits never straddles a word.
+__device__ __forceinline__ uint32_t exp_digit(const uint32_t *__restrict__ e, int ew, int j, int w) {
+    const int bit0 = j * w, wd = bit0 >> 5;
+    return wd < ew ? (e[wd] >> (bit0 & 31)) & ((1u << w) - 1u) : 0u;
+}
+
+// *maxbits = max(*maxbits, bit length of the largest exponent); one atomic per block that holds a nonzero one
+__global__ void k_exp_maxbits(const uint32_t *__restrict__ e, int ew, size_t count, int *__restrict__ maxbits) {
+    __shared__ int sm;
+    if (threadIdx.x == 0) sm = 0;
+    __syncthreads();
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) {
+        const uint32_t *r = e + i * (size_t)ew;
+        int bits = 0;
+        for (int wd = ew - 1; wd >= 0 && !bits; wd--)
+            if (r[wd]) bits = 32 * wd + 32 - __clz((int)r[wd]);
+        if (bits) atomicMax(&sm, bits);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && sm) atomicMax(maxbits, sm);
+}
+
+// The gather lists of a chunk of m rows whose table holds x^d at row (d - 1) m + i:
+// g[j m + i] = digit j of e[i] ? (digit - 1) m + i : -1 (the integer 1), for the nwin 4-bit windows.
+__global__ void k_exp_windows(const uint32_t *__restrict__ e, int ew, size_t m, int nwin, int64_t *__restrict__ g) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t *r = e + i * (size_t)ew;
+    for (int j = 0; j < nwin; j++) {
+        const uint32_t d = exp_digit(r, ew, j, 4);
+        g[(size_t)j * m + i] = d ? (int64_t)((size_t)(d - 1) * m + i) : -1;
+    }
+}
+
+// out[g] = idx[g] < 0 ? 1 : src[idx[g]] (rows of cw words); one thread per word
+__global__ void k_gather_rows(const uint32_t *__restrict__ src, const int64_t *__restrict__ idx, int cw, size_t count,
+                              uint32_t *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count * (size_t)cw) return;
+    const size_t g = t / (size_t)cw, w = t - g * (size_t)cw;
+    const int64_t r = idx[g];
+    out[t] = r < 0 ? (uint32_t)(w == 0) : src[(size_t)r * cw + w];
+}
+
+// out[0 .. count) = the integer 1
+__global__ void k_rows_one(int cw, size_t count, uint32_t *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < count * (size_t)cw) out[t] = (uint32_t)(t % (size_t)cw == 0);
+}
+
+// *bad = 1 when an index falls outside [0, rows)
+__global__ void k_idx_check(const int64_t *__restrict__ idx, size_t n, size_t rows, int *__restrict__ bad) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n && (idx[t] < 0 || (size_t)idx[t] >= rows)) *bad = 1;
+}
+
+// Term t of the dot product: its segment s (seg[s] <= t < seg[s + 1], by binary search; empty segments are
+// stepped over) and, when s lies in the chunk [s0, s0 + ns), its buckets: digit d != 0 of window j goes to
+// bucket ((s - s0) nwin + j) D + (D - d), digits descending inside a (segment, window).
+__device__ __forceinline__ bool dot_term(const int64_t *__restrict__ seg, size_t nseg, size_t s0, size_t ns, size_t t,
+                                         size_t &s_rel) {
+    size_t lo = 0, hi = nseg;                 // smallest s with seg[s + 1] > t
+    while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        if (seg[mid + 1] > (int64_t)t) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= nseg || lo < s0 || lo >= s0 + ns) return false;
+    s_rel = lo - s0;
+    return true;
+}
+
+__global__ void k_dot_count(const uint32_t *__restrict__ e, int ew, const int64_t *__restrict__ seg, size_t nseg,
+                            size_t terms, size_t s0, size_t ns, int w, int nwin, unsigned long long *__restrict__ cnt) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= terms) return;
+    size_t s;
+    if (!dot_term(seg, nseg, s0, ns, t, s)) return;
+    const uint32_t *r = e + t * (size_t)ew;
+    const size_t D = ((size_t)1 << w) - 1;
+    for (int j = 0; j < nwin; j++) {
+        const uint32_t d = exp_digit(r, ew, j, w);
+        if (d) atomicAdd(&cnt[(s * nwin + j) * D + (D - d)], 1ull);
+    }
+}
+
+__global__ void k_dot_scatter(const uint32_t *__restrict__ e, int ew, const int64_t *__restrict__ seg, size_t nseg,
+                              size_t terms, size_t s0, size_t ns, int w, int nwin, const int64_t *__restrict__ idx,
+                              const int64_t *__restrict__ bptr, unsigned long long *__restrict__ cursor,
+                              int64_t *__restrict__ bidx) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= terms) return;
+    size_t s;
+    if (!dot_term(seg, nseg, s0, ns, t, s)) return;
+    const uint32_t *r = e + t * (size_t)ew;
+    const size_t D = ((size_t)1 << w) - 1;
+    const int64_t row = idx ? idx[t] : (int64_t)t;
+    for (int j = 0; j < nwin; j++) {
+        const uint32_t d = exp_digit(r, ew, j, w);
+        if (!d) continue;
+        const size_t b = (s * nwin + j) * D + (D - d);
+        const unsigned long long pos = atomicAdd(&cursor[b], 1ull);
+        bidx[bptr[b] + (int64_t)pos] = row;
+    }
+}
+
+// One pass of the bucket products: of the G planned groups (gidx as k_plan_groups writes it, K lists of G) only
+// those with two members or more need products.  They are compacted, in any order, into cg (K lists, G apart,
+// *count entries each); where[g] says what group g becomes: a row of the source (>= 0, its only member), the
+// integer 1 (-1, no member) or product -where[g] - 2 of the compacted groups.
+__global__ void k_dot_active(const int64_t *__restrict__ gidx, size_t G, int K, unsigned long long *__restrict__ count,
+                             int64_t *__restrict__ cg, int64_t *__restrict__ where) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= G) return;
+    if (gidx[G + g] < 0) { where[g] = gidx[g]; return; }
+    const size_t a = (size_t)atomicAdd(count, 1ull);
+    for (int j = 0; j < K; j++) cg[(size_t)j * G + a] = gidx[(size_t)j * G + g];
+    where[g] = -(int64_t)a - 2;
+}
+
+// out[g] = where[g] >= 0 ? src[where[g]] : where[g] == -1 ? 1 : prod[-where[g] - 2]; one thread per word
+__global__ void k_gather_rows2(const uint32_t *__restrict__ src, const uint32_t *__restrict__ prod,
+                               const int64_t *__restrict__ where, int cw, size_t count, uint32_t *__restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count * (size_t)cw) return;
+    const size_t g = t / (size_t)cw, w = t - g * (size_t)cw;
+    const int64_t r = where[g];
+    out[t] = r >= 0 ? src[(size_t)r * cw + w] : r == -1 ? (uint32_t)(w == 0) : prod[(size_t)(-r - 2) * cw + w];
+}
+
+// yi[i nsj + j ns + s] = (s nwin + j) D + i: position i of every (segment, window)'s buckets, in the plane
+// order (window-major) the Horner step reads
+__global__ void k_dot_digit_lists(size_t ns, int nwin, int D, int64_t *__restrict__ yi) {
+    const size_t nsj = ns * (size_t)nwin;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nsj * (size_t)D) return;
+    const size_t i = t / nsj, q = t - i * nsj, j = q / ns, s = q - j * ns;
+    yi[t] = (int64_t)((s * nwin + j) * (size_t)D + i);
+}
+
 }  // namespace fthe

@@ -649,6 +649,72 @@ class Paillier:
                    "sub_inv")
         return out
 
+    def _weight_words(self, mags, what):
+        """Non-negative Python integers -> (len, e_words) uint32 words, e_words the fewest that hold the largest."""
+        bits = max((m.bit_length() for m in mags), default=0)
+        ew = max(1, (bits + 31) // 32)
+        if ew > self.n_words:
+            raise ValueError(f"{what}: a weight of {bits} bits does not fit the key's {32 * self.n_words}")
+        raw = b"".join(m.to_bytes(4 * ew, "little") for m in mags)
+        return np.frombuffer(raw, dtype=np.uint32).reshape(len(mags), ew).copy(), ew
+
+    @staticmethod
+    def _weights(k):
+        return [int(v) for v in (k.tolist() if isinstance(k, np.ndarray) else k)]
+
+    def scalar_mul_rows(self, x, k):
+        """x[i]^k[i] mod n^2 (fthe_scalar_mul_rows): the plaintext k_i m_i, one weight per row.  k: Python ints
+        or an integer numpy array, of any sign; the words per exponent follow the largest magnitude.  Rows with
+        a negative weight are raised to its magnitude and then inverted by one batched inverse (invert_batch)
+        over that subset: such a row must be a unit mod n^2 (every honest ciphertext is), or the call fails
+        (FtheError, FTHE_ERR_ARG) and returns nothing."""
+        x = np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, self._cw())
+        ks = self._weights(k)
+        if len(ks) != len(x):
+            raise ValueError(f"scalar_mul_rows: {len(ks)} weights for {len(x)} rows")
+        e, ew = self._weight_words([abs(v) for v in ks], "scalar_mul_rows")
+        out = np.zeros_like(x)
+        _lib.check(self.lib.fthe_scalar_mul_rows(self._key, self.dev.ctx, _ptr(x), _ptr(e), ew, len(x), _ptr(out)),
+                   "scalar_mul_rows")
+        neg = np.array([i for i, v in enumerate(ks) if v < 0], dtype=np.int64)
+        if len(neg):
+            out[neg] = self.invert_batch(out[neg])
+        return out
+
+    def _dot_unsigned(self, x, mags, seg, ix):
+        e, ew = self._weight_words(mags, "dot_segments")
+        out = np.zeros((len(seg) - 1, self._cw()), dtype=np.uint32)
+        _lib.check(self.lib.fthe_dot_segments(self._key, self.dev.ctx, _ptr(x), len(x), _ptr(e), ew, _ptr(seg),
+                                              _ptr(ix), len(seg) - 1, _ptr(out)), "dot_segments")
+        return out
+
+    def dot_segments(self, x, k, seg_ptr, idx=None, offset=None):
+        """out[s] = prod x[idx[t]]^k[t] over t in [seg_ptr[s], seg_ptr[s+1]) mod n^2 (fthe_dot_segments): the
+        plaintext sum_t k_t m_t (+ offset) mod n.  k: one weight per term, Python ints or an integer numpy array,
+        of any sign.  With a negative weight, or an offset, the positive parts and the magnitudes of the negative
+        parts (zeroes where the other has weight) go through two calls and sub_inv_batch(P_pos, P_neg, offset)
+        joins them; offset is fthe_sub_inv's public constant that keeps the plaintext non-negative for the
+        existing decoders.  A segment whose negative part is no unit mod n^2 fails the whole call (FtheError,
+        FTHE_ERR_ARG), as fthe_sub_inv documents, and nothing is returned."""
+        x = np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, self._cw())
+        seg = np.ascontiguousarray(seg_ptr, dtype=np.int64)
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        ks = self._weights(k)
+        terms = int(seg[-1]) if len(seg) else 0
+        if len(ks) != terms:
+            raise ValueError(f"dot_segments: {len(ks)} weights for {terms} terms")
+        if not offset and all(v >= 0 for v in ks):
+            return self._dot_unsigned(x, ks, seg, ix)
+        pos = self._dot_unsigned(x, [max(v, 0) for v in ks], seg, ix)
+        neg = self._dot_unsigned(x, [max(-v, 0) for v in ks], seg, ix)
+        return self.sub_inv_batch(pos, neg, offset)
+
+    def dot_plan(self, e_bits, terms, nseg):
+        """The form fthe_dot_segments takes unforced: 0 (composed), 4 or 8 (fthe_debug_dot_plan)."""
+        w = ctypes.c_int(-1)
+        _lib.check(self.lib.fthe_debug_dot_plan(int(e_bits), int(terms), int(nseg), ctypes.byref(w)), "dot_plan")
+        return w.value
+
     def direct_y(self, seed, index0, count):
         """(y_p, y_q) words ((count, pq_words) uint32 each) that encrypt_u64[_dev](r=None, seed=seed)
         draws for ciphertexts [index0, index0 + count) on the key holder's direct-y path
@@ -851,6 +917,29 @@ class Paillier:
         _lib.check(self.lib.fthe_sub_inv_dev(self._key, self.dev.ctx, ctypes.c_void_p(a.data_ptr()),
                                              ctypes.c_void_p(b.data_ptr()), cnt, off, ow,
                                              ctypes.c_void_p(out.data_ptr())), "sub_inv_dev")
+        return out
+
+    @_stream_ordered
+    def scalar_mul_rows_dev(self, x, e, out):
+        """fthe_scalar_mul_rows_dev on device rows: out[i] = x[i]^e[i]; e: device (count, e_words) words, unsigned;
+        out may be x.  One read-back (the largest exponent's bit length)."""
+        cnt = x.numel() // self._cw()
+        ew = e.numel() // cnt if cnt else 1
+        _lib.check(self.lib.fthe_scalar_mul_rows_dev(self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()),
+                                                     ctypes.c_void_p(e.data_ptr()), int(ew), cnt,
+                                                     ctypes.c_void_p(out.data_ptr())), "scalar_mul_rows_dev")
+        return out
+
+    @_stream_ordered
+    def dot_segments_dev(self, x, e, seg_ptr, out, idx=None):
+        """fthe_dot_segments_dev: device x (rows, 2nw), e (terms, e_words) unsigned words, int64 seg_ptr and
+        optional int64 idx; out (nseg, 2nw) aliases no input."""
+        rows = x.numel() // self._cw()
+        ew = e.shape[-1] if e.dim() > 1 else 1
+        _lib.check(self.lib.fthe_dot_segments_dev(
+            self._key, self.dev.ctx, ctypes.c_void_p(x.data_ptr()), rows, ctypes.c_void_p(e.data_ptr()), int(ew),
+            ctypes.c_void_p(seg_ptr.data_ptr()), ctypes.c_void_p(idx.data_ptr()) if idx is not None else None,
+            seg_ptr.numel() - 1, ctypes.c_void_p(out.data_ptr())), "dot_segments_dev")
         return out
 
     @_stream_ordered

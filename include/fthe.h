@@ -528,6 +528,45 @@ int fthe_sub_inv_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint
 int fthe_sub_inv(fthe_key *key, fthe_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t count,
                  const uint32_t *offset, int offset_words, uint32_t *out);
 
+/* ---- plaintext weights per row: Enc(m_i)^(k_i) and weighted segment sums (opt-in; not in the reference) ----
+ * fthe_scalar_mul_rows  out[i] = x[i]^(e[i]) mod n^2: the plaintext k_i m_i.  e holds count x e_words little-endian
+ *                       words, unsigned; 1 <= e_words <= n_words, else FTHE_ERR_ARG.  x^0 = 1, 0^0 included.  Alias-
+ *                       safe: out may be exactly x.  Fixed 4-bit windows on a table x^1 .. x^15 per chunk of 2^17
+ *                       rows (FTHE_ROWS_CHUNK overrides, read per call; fewer when fthe_ctx_set_mem_limit does not
+ *                       admit the table of 15 rows per row): 14 + 5 (ceil(B / 4) - 1) products mod n^2 per row, B the
+ *                       bit length of the call's largest exponent (one read-back per call); B = 0 writes ones
+ *                       with no product.
+ * fthe_dot_segments     out[s] = prod_{t in [seg_ptr[s], seg_ptr[s+1])} x[idx ? idx[t] : t]^(e[t]) mod n^2: the plaintext
+ *                       sum_t e_t m_t mod n, one exponent per term t.  As fthe_reduce_segments_csr_dev: seg_ptr (nseg + 1
+ *                       int64), idx (int64, or NULL for the identity) and e are device arrays in the _dev form and
+ *                       host arrays in the other; seg_ptr[nseg] is read back once; an empty segment, or one whose
+ *                       weights are all 0, gives the integer 1; out aliases no input.  x holds x_rows rows; an idx
+ *                       entry outside [0, x_rows) fails the call with FTHE_ERR_ARG.  Three forms with the same rows,
+ *                       picked by a product-count model (fthe_debug_dot_plan; FTHE_DOT_WINDOW=0|4|8, read per call,
+ *                       forces one): 0 = fthe_scalar_mul_rows on the gathered terms, then the segmented product;
+ *                       4 / 8 = buckets (Pippenger) of that window width: per (segment, window, digit) the product
+ *                       of the terms with that digit, by the segmented product's passes over the groups that hold
+ *                       two rows or more; the digit weights by a running product down the digits, 2 (2^w - 2)
+ *                       products per (segment, window); Horner across the windows.  Segments are taken in chunks whose bucket rows fit 1 GiB or the context's cap
+ *                       (FTHE_DOT_SEG_CHUNK overrides, read per call).
+ *   - Rows are canonical (< n^2) and so is the result; both forms of a call give the same bytes.
+ *   - Any key with the public form may call them (every key size of fthe_scalar_mul_u64); no private key is needed.
+ *   - count == 0 / nseg == 0: FTHE_OK.  The host forms stage through the context's device buffers.
+ *   - The exponents are unsigned.  A negative weight is x^-1 raised to its magnitude: fthe_invert / fthe_sub_inv on
+ *     the results (fedtree_amd/paillier.py composes that), one batched inverse over the outputs.
+ *   - fthe_last_kernel_ms / fthe_last_montmuls cover the whole call, all inner passes summed.
+ * fthe_debug_dot_plan   host only: the form fthe_dot_segments takes unforced for exponents of at most e_bits bits,
+ *                       `terms` terms and nseg segments (0, 4 or 8; tools/dot_model.py dot_plan is the same model). */
+int fthe_scalar_mul_rows_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, const uint32_t *e, int e_words,
+                             size_t count, uint32_t *out);
+int fthe_scalar_mul_rows(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, const uint32_t *e, int e_words,
+                         size_t count, uint32_t *out);
+int fthe_dot_segments_dev(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t x_rows, const uint32_t *e,
+                          int e_words, const int64_t *seg_ptr, const int64_t *idx, size_t nseg, uint32_t *out);
+int fthe_dot_segments(fthe_key *key, fthe_ctx *ctx, const uint32_t *x, size_t x_rows, const uint32_t *e,
+                      int e_words, const int64_t *seg_ptr, const int64_t *idx, size_t nseg, uint32_t *out);
+int fthe_debug_dot_plan(int e_bits, size_t terms, size_t nseg, int *window);
+
 /* ---- slot-packed pairs: several (g, h) bins in one ciphertext (opt-in; not in the reference) ----
  * A pair-packed ciphertext (above) uses W = 192 plaintext bits of a key's thousands.  A slot-packed
  * one holds `slots` such plaintexts T_j, each in a slot of slot_bits bits:
