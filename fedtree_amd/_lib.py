@@ -52,6 +52,7 @@ _PROTOS = {
     "fthe_ctx_set_mem_limit": (_I, [_P, _SZ]),
     "fthe_host_alloc": (_I, [_SZ, _PP]),
     "fthe_debug_addb_image": (_I, [_P, _I, _P, _SZ, _P]),
+    "fthe_debug_mul192_image": (_I, [_P, _I, _P, _SZ, _P]),
     "fthe_debug_nadicb_image": (_I, [_P, _I, _P, _SZ, _P]),
     "fthe_debug_nadicb_prog": (_I, [_P, _P, _P, _I, _P, _I, _SZ, _I, _P]),
     "fthe_debug_padic_prog": (_I, [_P, _P, _I, _P, _I, _P, _I, _SZ, _I, _P]),

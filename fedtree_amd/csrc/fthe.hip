@@ -35,6 +35,7 @@
 #include "group_commit.hpp"
 #include "padic_tiles.hpp"
 #include "addb_image.hpp"
+#include "mul192_image.hpp"
 #include "nadicb_image.hpp"
 #include "fthe_glue.h"
 #include "gen/montprog_blobs.h"
@@ -441,6 +442,7 @@ struct fthe_key {
         if (d_nwords) (void)hipFree(d_nwords);
         if (d_pqwords) (void)hipFree(d_pqwords);
         if (d_addb) (void)hipFree(d_addb);
+        if (d_mul192) (void)hipFree(d_mul192);
         for (uint32_t *p : {fb.d_tab_pub, fb.d_tab_p, fb.d_tab_q, fb.d_prog}) if (p) (void)hipFree(p);
         for (uint32_t *p : {xb.d_tab[0], xb.d_tab[1], xb.d_prog}) if (p) (void)hipFree(p);
         if (pb.d_prog) (void)hipFree(pb.d_prog);           // pb.tab: shared, freed by its last key
@@ -475,6 +477,9 @@ struct fthe_key {
     bool rowio = false;
     bool add_classical = false;               // pr_add_w is one classical product (no R^2 constant)
     void *d_addb = nullptr;                   // fthe_addb_q152's per-key context (addb_image.hpp): n of 2048 bits
+    // fthe_mul192's per-key context (mul192_image.hpp): n of 96 words.  Such a key has no op-program kernel mod n^2
+    // (pub_ok stays false): add, k-way product and the uniform scalar mul run on fthe_mul192, nothing else does
+    void *d_mul192 = nullptr;
     PH pr_enc_pub, pr_add, pr_sub, pr_enc_p, pr_enc_q, pr_enc_p_nt, pr_enc_tail, pr_dec_pl, pr_dec_ql, pr_enc_pl, pr_enc_ql, pr_dec_p, pr_dec_q, pr_dec_hp, pr_dec_hq, pr_dec_t;
     PH pr_encA_p, pr_encA_q;      // stage A of the CRT encrypt (mod p, q; small kernel)
     // P-adic form of stage B: the exponentiation (P-adic kernel), then the rest on s74
@@ -923,7 +928,14 @@ static int key_finish(fthe_key *k) {
     }
     k->sn2 = kernel_shape_for_bits((int)k->n2.bits());
     k->pub_ok = k->sn2.S != 0;
-    if (!k->pub_ok && !k->priv) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && k->n_words == mul192::kWords / 2) {
+        std::vector<uint8_t> img;
+        if (mul192::build(k->n, img)) {
+            if (hipMalloc(&k->d_mul192, img.size()) != hipSuccess) return FTHE_ERR_NOMEM;
+            HIPOK(hipMemcpy(k->d_mul192, img.data(), img.size(), hipMemcpyHostToDevice));
+        }
+    }
+    if (!k->pub_ok && !k->priv && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     Mpz one(1);
 
     if (k->pub_ok) {
@@ -3615,6 +3627,118 @@ static int launch_addb_pair(fthe_ctx *c, const fthe_key *k, const uint32_t *x, c
     return FTHE_OK;
 }
 
+// ---- Paillier-3072: products of 192-word rows on fthe_mul192 (fthe_mul192.hip) ----
+// out = x y mod n^2 for count rows; x or y null: the integer 1.  out may be exactly x or y.
+static int launch_mul192(fthe_ctx *c, const fthe_key *k, const uint32_t *x, const uint32_t *y, uint32_t *out,
+                         size_t count) {
+    // launches of at most 4M rows: row * 768 stays below 2^32
+    constexpr size_t kMaxRows = (size_t)1 << 22;
+    for (size_t off = 0; off < count; off += kMaxRows) {
+        const size_t o = off * mul192::kWords;
+        if (mul192::launch(c->stream, x ? x + o : nullptr, y ? y + o : nullptr, out + o, k->d_mul192,
+                           std::min(kMaxRows, count - off), c->n_cu) != hipSuccess)
+            return FTHE_ERR_HIP;
+    }
+    return FTHE_OK;
+}
+// A call on fthe_mul192 has no slots: begin_call's device check, then (the context's device being current, as for
+// every allocation of a call) scratch bytes of c->scratch under the cap of fthe_ctx_set_mem_limit, as begin_call
+// holds the slot region under it, then the time mark; end_call's accounting.
+static int mul192_begin(fthe_ctx *c, const fthe_key *k, size_t scratch = 0) {
+    if (k->device != c->device) return FTHE_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (scratch) {
+        if (c->mem_limit && scratch > c->mem_limit && scratch > c->scratch.n) return FTHE_ERR_NOMEM;
+        if (int rc = c->scratch.ensure(scratch)) return rc;
+    }
+    return mark_start(c);
+}
+// rows per chunk of a host-resident add: the row-I/O add's footprint per chunk; FTHE_MUL192_CHUNK overrides (read
+// per call: chunk-boundary tests)
+static size_t mul192_chunk_rows() {
+    const char *e = getenv("FTHE_MUL192_CHUNK");
+    const size_t r = e ? (size_t)strtoull(e, nullptr, 10) : chunk_lanes() / 4 * 128 / mul192::kWords;
+    return std::max<size_t>(256, (r + 255) / 256 * 256);
+}
+static int mul192_end(fthe_ctx *c, double products) {
+    Launch Lc;
+    Lc.mm = products;
+    return end_call(c, Lc);
+}
+// the add: device rows in one persistent launch; host rows (pipe) in chunks of the row-I/O add's footprint
+static int mul192_pair(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out,
+                       HostPipe *pipe) {
+    int rc = mul192_begin(c, k);
+    if (rc) return rc;
+    if (!pipe) {
+        if ((rc = launch_mul192(c, k, a, b, out, count))) return rc;
+        return mul192_end(c, (double)count);
+    }
+    const size_t L = mul192_chunk_rows(), cw = mul192::kWords;
+    for (size_t off = 0; off < count; off += L) {
+        const size_t cnt = std::min(L, count - off);
+        if ((rc = pipe->before(off, L, count))) return rc;
+        if ((rc = launch_mul192(c, k, a + off * cw, b + off * cw, out + off * cw, cnt))) return rc;
+        if ((rc = pipe->after(off, cnt))) return rc;
+    }
+    return mul192_end(c, (double)count);
+}
+// the k-way product as a chain: out = x_0 x_1, then out = out x_j (kk = 1: x_0 times 1, which reduces it).  out may be
+// exactly x_0 or x_1 and must not overlap a later plane; otherwise the chain runs in c->scratch and is copied out.
+static int mul192_kway(fthe_key *k, fthe_ctx *c, const uint32_t *const *xs, int kk, size_t count, uint32_t *out) {
+    const size_t bytes = count * mul192::kWords * 4;
+    bool direct = true;
+    for (int j = 0; j < kk; j++) {
+        const char *o = (const char *)out, *x = (const char *)xs[j];
+        direct = direct && (o + bytes <= x || x + bytes <= o || (j < 2 && o == x));
+    }
+    int rc = mul192_begin(c, k, direct ? 0 : bytes);
+    if (rc) return rc;
+    uint32_t *acc = direct ? out : (uint32_t *)c->scratch.p;
+    if ((rc = launch_mul192(c, k, xs[0], kk > 1 ? xs[1] : nullptr, acc, count))) return rc;
+    for (int j = 2; j < kk; j++)
+        if ((rc = launch_mul192(c, k, acc, xs[j], acc, count))) return rc;
+    if (!direct && count) HIPOK(hipMemcpyAsync(out, acc, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return mul192_end(c, (double)count * std::max(kk - 1, 1));
+}
+// x^e for one exponent, left to right in binary over whole-batch launches; x is kept in c->scratch, so out may be x
+static int mul192_pow(fthe_key *k, fthe_ctx *c, const uint32_t *x, const mpz_t e, size_t count, uint32_t *out) {
+    const size_t bytes = count * mul192::kWords * 4;
+    int rc = mul192_begin(c, k, mpz_sgn(e) ? bytes : 0);                             // e = 0 keeps no copy of x
+    if (rc) return rc;
+    if (mpz_sgn(e) == 0) {
+        if ((rc = launch_mul192(c, k, nullptr, nullptr, out, count))) return rc;      // 1 * 1
+        return mul192_end(c, (double)count);
+    }
+    uint32_t *base = (uint32_t *)c->scratch.p;
+    if (count) HIPOK(hipMemcpyAsync(base, x, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if ((rc = launch_mul192(c, k, base, nullptr, out, count))) return rc;               // x mod n^2
+    double products = 1;
+    for (size_t i = mpz_sizeinbase(e, 2) - 1; i-- > 0;) {
+        if ((rc = launch_mul192(c, k, out, out, out, count))) return rc;
+        products += 1;
+        if (mpz_tstbit(e, i)) {
+            if ((rc = launch_mul192(c, k, out, base, out, count))) return rc;
+            products += 1;
+        }
+    }
+    return mul192_end(c, (double)count * products);
+}
+
+// Test hook (include/fthe.h): the per-key context bytes of fthe_mul192, host only.
+extern "C" int fthe_debug_mul192_image(const uint32_t *n, int n_words, uint8_t *out, size_t cap, size_t *len) {
+    if (!n || n_words <= 0 || !len) return FTHE_ERR_ARG;
+    Mpz nn;
+    mpz_import(nn, (size_t)n_words, -1, 4, 0, 0, n);
+    std::vector<uint8_t> img;
+    if (!mul192::build(nn, img)) return FTHE_ERR_UNSUPPORTED;
+    *len = img.size();
+    if (!out) return FTHE_OK;
+    if (cap < img.size()) return FTHE_ERR_ARG;
+    memcpy(out, img.data(), img.size());
+    return FTHE_OK;
+}
+
 // Test hook (include/fthe.h): the per-key context bytes of fthe_addb_q152, host only.
 extern "C" int fthe_debug_addb_image(const uint32_t *n, int n_words, uint8_t *out, size_t cap, size_t *len) {
     if (!n || n_words <= 0 || !len) return FTHE_ERR_ARG;
@@ -3762,6 +3886,7 @@ extern "C" int fthe_debug_nadicb_image(const uint32_t *n, int n_words, uint8_t *
 static int pair_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out,
                      HostPipe *pipe, int sub_bits) {
     if (!k || !c || ((!a || !b || !out) && count)) return FTHE_ERR_ARG;
+    if (k->d_mul192 && !sub_bits) return mul192_pair(k, c, a, b, count, out, pipe);
     if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
     const bool sub = sub_bits != 0, dyn = sub && sub_bits != 64;
     if (sub && (sub_bits < 8 || sub_bits > 32 * k->n_words)) return FTHE_ERR_ARG;
@@ -3935,6 +4060,7 @@ extern "C" int fthe_reduce_kway_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x,
     if (!k || kk <= 0 || kk > 64 || (!x && count)) return FTHE_ERR_ARG;
     std::vector<const uint32_t *> xs(kk);
     for (int j = 0; j < kk; j++) xs[j] = x + (size_t)j * count * 2 * k->n_words;
+    if (k->d_mul192) return c && (out || !count) ? mul192_kway(k, c, xs.data(), kk, count, out) : FTHE_ERR_ARG;
     Mpz Rk; mpz_powm_ui(Rk, k->mn2.m.R, (unsigned long)kk, k->n2);
     return rowprod_impl(k, c, xs.data(), kk, count, out, Rk, true);
 }
@@ -4551,6 +4677,7 @@ extern "C" int fthe_scan_segments(fthe_key *k, fthe_ctx *c, const uint32_t *x, c
 // x^e mod n^2 for one exponent e shared by the batch (Paillier::mul, paillier.cpp:107-120)
 static int scalar_mul_impl(fthe_key *k, fthe_ctx *c, const uint32_t *x, const mpz_t ez, size_t count, uint32_t *out) {
     if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
+    if (k->d_mul192) return mul192_pow(k, c, x, ez, count, out);
     if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
     Launch Lc;
     int rc = begin_call(c, k, count, Lc, nslots_for(k), k->sn2);

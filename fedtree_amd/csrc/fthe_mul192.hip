@@ -1,0 +1,251 @@
+// fthe_mul192: out[g] = x[g] y[g] mod N for N = n^2 of a Paillier-3072 key (n of 3041..3072 bits, N of 6081..6144),
+// canonical little-endian rows of 192 dwords in and out, any row value accepted (rows >= N too), the result in
+// [0, N).  tools/mul192_model.py is the bit-exact model of the arithmetic, DESIGN.md 22 the write-up.
+//
+// Eight lanes per ciphertext (lane l of the octet owns limbs [29 l, 29 l + 29) of 27 bits: 232 limbs), eight
+// ciphertexts per wave, eight waves per workgroup, one persistent workgroup per CU; its waves take batches of
+// eight rows from a counter in LDS.
+//
+//   1. rows -> LDS -> limbs: x in registers, y as the octet's multiplier column in LDS.
+//   2. z = x y by operand scanning: step s multiplies the lane's 29 limbs by y[s] (one LDS broadcast) into a ring
+//      of 29 64-bit columns (lane l holds columns 29 l + s .. 29 l + s + 28); the lowest column is complete for the
+//      lane and moves one lane down by DPP (lane 7 takes a fresh 0), lane 0's retires as limb s of z through a
+//      carry chain into the LDS word whose multiplier was just consumed.  A column sums at most 232 products
+//      below 2^54: no carry is needed before a column retires.  232 more steps without products drain the ring.
+//   3. Barrett on the VALU with the same routine: q = ((z >> 27*225) mu) >> 27*231 with mu = floor(2^12312 / N)
+//      is floor(z / N) or one less, then r = (z - q N) mod 2^(27*228) in [0, 2N): the third
+//      product retires its limbs straight into the borrow chain of z - q N.
+//   4. r -> dwords (lane l: dwords [24 l, 24 l + 24); r < 2N may have bit 6144 set, which stays in its limb), one
+//      conditional subtraction of N mod 2^6144 with the borrow resolved across the octet, rows stored.  Every operand row of a batch is loaded before any is stored.
+#include <algorithm>
+#include <utility>
+
+#include "mul192_image.hpp"
+
+namespace mul192 {
+namespace {
+
+constexpr uint32_t kMask = (1u << kLimbBits) - 1;
+constexpr int kRowStride = 2 * kLimbs + 1;     // LDS words per ciphertext: 464 limbs; odd: the rows of a wave
+                                               // land in distinct banks
+constexpr int kStage = kLimbs;                 // an operand row's dwords are staged at words [232, 232 + 196)
+constexpr int kCtxWords = kCtxBytes / 4;
+constexpr int kRLimbs = 228;                   // r < 2N < 2^(27 * 228)
+enum { kFull = 0, kHigh = 1, kSub = 2 };
+
+// f(integral_constant<int, 0>) .. f(integral_constant<int, N - 1>): the ring of columns is indexed by constants only
+template <class F, int... I>
+__device__ inline void static_for(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ inline void static_for(F &&f) {
+    static_for(f, std::make_integer_sequence<int, N>{});
+}
+
+__device__ inline void wave_sync() {           // LDS written by one lane of the wave, read by another
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the value of the next lane of the octet; 0 in its top lane
+__device__ inline uint64_t from_above(uint64_t v, bool top) {
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, 0x101, 0xf, 0xf, true);          // row_shl:1
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x101, 0xf, 0xf, true);
+    return top ? 0 : ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// The 464 limbs of x m (m: 232 multiplier limbs in LDS) through lane 0's carry chain into area:
+//   kFull  all of them (m may be area itself: limb s lands on multiplier s after it was read);
+//   kHigh  limbs 231 .. 463 only (area[0, 228) is kept);
+//   kSub   area[s] = limb s of (area - x m) mod 2^(27 * 228), zero up to limb 231; no high half.
+template <int MODE>
+__device__ inline void product(const uint32_t (&x)[kPerLane], const uint32_t *m, uint32_t *area, bool lane0, bool top) {
+    uint64_t acc[kPerLane];
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) acc[i] = 0;
+    uint64_t carry = 0;
+    uint32_t borrow = 0;
+#pragma unroll 1
+    for (int b = 0; b < kLanes; b++) {
+        const uint32_t *mb = m + kPerLane * b;
+        uint32_t *ob = area + kPerLane * b;
+        static_for<kPerLane>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            const uint32_t ys = mb[t];
+            static_for<kPerLane>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                acc[(t + i) % kPerLane] += (uint64_t)x[i] * ys;
+            });
+            carry += acc[t];
+            uint32_t limb = (uint32_t)carry & kMask;
+            carry >>= kLimbBits;
+            if (MODE == kSub) {
+                const uint32_t d = ob[t] - limb - borrow;
+                borrow = d >> 31;
+                limb = kPerLane * b + t < kRLimbs ? d & kMask : 0;
+            }
+            if (lane0 && (MODE != kHigh || kPerLane * b + t >= kShiftB)) ob[t] = limb;
+            acc[t] = from_above(acc[t], top);
+        });
+    }
+    if (MODE == kSub) return;
+#pragma unroll 1
+    for (int b = 0; b < kLanes; b++) {
+        uint32_t *ob = area + kLimbs + kPerLane * b;
+        static_for<kPerLane>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            carry += acc[t];
+            if (lane0) ob[t] = (uint32_t)carry & kMask;
+            carry >>= kLimbBits;
+            acc[t] = from_above(acc[t], top);
+        });
+    }
+}
+
+// a row's dwords (lane l holds the 16-byte pieces 8 k + l) -> the staging words, zero padded for the limb reads
+__device__ inline void stage(uint32_t *area, const uint4 (&v)[6], int l) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        uint32_t *p = area + kStage + 4 * (8 * k + l);
+        p[0] = v[k].x; p[1] = v[k].y; p[2] = v[k].z; p[3] = v[k].w;
+    }
+    if (l < 4) area[kStage + kWords + l] = 0;
+}
+
+// The lane index as a value the compiler cannot trace to the loop's invariants: the bit offsets and word indices
+// derived from it are then computed where they are used, not hoisted out of the batch loop and kept (spilled)
+// across the three products.
+__device__ inline int opaque(int l) {
+    asm volatile("" : "+v"(l));
+    return l;
+}
+
+// the lane's 29 limbs of the staged row
+__device__ inline void limbs_of(const uint32_t *area, int l, uint32_t (&x)[kPerLane]) {
+    l = opaque(l);
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) {
+        const uint32_t bit = (uint32_t)kLimbBits * (uint32_t)(kPerLane * l + i), w = bit >> 5;
+        const uint64_t v = (uint64_t)area[kStage + w] | (uint64_t)area[kStage + w + 1] << 32;
+        x[i] = (uint32_t)(v >> (bit & 31)) & kMask;
+    }
+}
+
+__device__ inline void load_row(const uint32_t *base, uint64_t row, int l, uint4 (&v)[6]) {
+    if (base) {
+        const uint4 *p = (const uint4 *)(base + row * kWords);
+#pragma unroll
+        for (int k = 0; k < 6; k++) v[k] = p[8 * k + l];
+    } else {                                   // the integer 1
+#pragma unroll
+        for (int k = 0; k < 6; k++) v[k] = make_uint4(0, 0, 0, 0);
+        if (l == 0) v[0].x = 1;
+    }
+}
+
+__global__ __launch_bounds__(64 * kWaves) void fthe_mul192_kernel(const uint32_t *x, const uint32_t *y, uint32_t *out,
+                                                                  const uint32_t *kctx, uint32_t count, uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint32_t nbatch = (count + kRowsPerWave - 1) / kRowsPerWave;
+    for (;;) {
+        // workgroup wg owns batches wg, wg + nwg, ...; its waves take them in turn
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&s_next, 1u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        const uint64_t batch = blockIdx.x + (uint64_t)t * nwg;
+        if (batch >= nbatch) break;
+        uint64_t row = batch * kRowsPerWave + oct;
+        const bool live = row < count;
+        if (!live) row = count - 1;            // an idle octet repeats the last row and stores nothing
+        // one operand at a time through the staging words (few registers live at once); both are loaded before
+        // the batch stores anything
+        uint4 v[6];
+        uint32_t xl[kPerLane];
+        load_row(y, row, l, v);
+        stage(area, v, l);
+        load_row(x, row, l, v);
+        wave_sync();
+        limbs_of(area, l, xl);                 // y's limbs: the multiplier column (not the staging words)
+#pragma unroll
+        for (int i = 0; i < kPerLane; i++) area[kPerLane * l + i] = xl[i];
+        wave_sync();
+        stage(area, v, l);
+        wave_sync();
+        limbs_of(area, l, xl);
+        wave_sync();
+        product<kFull>(xl, area, area, lane0, top);                     // z
+        wave_sync();
+#pragma unroll
+        for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftA + kPerLane * l + i];
+        wave_sync();
+        product<kHigh>(xl, s_mu, area, lane0, top);                     // (z >> 27*225) mu
+        wave_sync();
+#pragma unroll
+        for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftB + kPerLane * l + i];
+        wave_sync();
+        product<kSub>(xl, s_nl, area, lane0, top);                      // r = z - q N
+        wave_sync();
+        uint32_t r[24];
+        const int lo = opaque(l);
+        const uint32_t *nd = s_nd + 24 * lo;
+#pragma unroll
+        for (int k = 0; k < 24; k++) {
+            const uint32_t bit = 32u * (uint32_t)(24 * lo + k), j = bit / kLimbBits;
+            const uint64_t v = (uint64_t)area[j] | (uint64_t)area[j + 1] << 27 | (uint64_t)area[j + 2] << 54;
+            r[k] = (uint32_t)(v >> (bit - kLimbBits * j));
+        }
+        // r - N: the lane's own borrow g, and whether a borrow from below passes through (the difference is 0)
+        uint32_t g = 0, any = 0;
+#pragma unroll
+        for (int k = 0; k < 24; k++) {
+            const uint64_t d = (uint64_t)r[k] - nd[k] - g;
+            g = (uint32_t)(d >> 63);
+            any |= (uint32_t)d;
+        }
+        const uint32_t pass = any == 0 ? 1u : 0u;
+        uint32_t bin = 0, bout = g;
+#pragma unroll
+        for (int it = 0; it < kLanes - 1; it++) {
+            const uint32_t up = __shfl_up(bout, 1, kLanes);
+            bin = lane0 ? 0u : up;
+            bout = g | (bin & pass);
+        }
+        // r < N: the octet's last borrow, unless r has bits above the row (r < 2N may reach 2^6144: limb 227, bit 15)
+        const bool keep = __shfl(bout, kLanes - 1, kLanes) != 0 && (area[kRLimbs - 1] >> (32 * kWords % kLimbBits)) == 0;
+#pragma unroll
+        for (int k = 0; k < 24; k++) {
+            const uint64_t d = (uint64_t)r[k] - nd[k] - bin;
+            bin = (uint32_t)(d >> 63);
+            r[k] = keep ? r[k] : (uint32_t)d;
+        }
+        if (live) {
+            uint4 *p = (uint4 *)(out + row * kWords + 24 * l);
+#pragma unroll
+            for (int k = 0; k < 6; k++) p[k] = make_uint4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+        }
+        wave_sync();
+    }
+}
+
+}  // namespace
+
+int launch(hipStream_t st, const uint32_t *x, const uint32_t *y, uint32_t *out, const void *kctx, size_t count, int n_cu) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<size_t>((count + kPerWg - 1) / kPerWg, (size_t)std::max(n_cu, 1));
+    hipLaunchKernelGGL(fthe_mul192_kernel, dim3(blocks), dim3(64 * kWaves), 0, st, x, y, out, (const uint32_t *)kctx,
+                       (uint32_t)count, blocks);
+    return hipGetLastError();
+}
+
+}  // namespace mul192

@@ -886,6 +886,21 @@ class Paillier:
         return out
 
     @_stream_ordered
+    def scalar_mul_dev(self, x, k, out):
+        """x^k mod n^2 on device rows for one k >= 0 of any size (fthe_scalar_mul_u64_dev / _words_dev); out may be x."""
+        k, cnt = int(k), x.numel() // self._cw()
+        if k < 0:
+            raise ValueError("exponent must be non-negative")
+        xp, op = ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr())
+        if k < 2**64:
+            _lib.check(self.lib.fthe_scalar_mul_u64_dev(self._key, self.dev.ctx, xp, k, cnt, op), "scalar_mul_dev")
+        else:
+            ew = _words(k, (k.bit_length() + 31) // 32)
+            _lib.check(self.lib.fthe_scalar_mul_words_dev(self._key, self.dev.ctx, xp, _ptr(ew), len(ew), cnt, op),
+                       "scalar_mul_dev")
+        return out
+
+    @_stream_ordered
     def sub_dev(self, a, b, out):
         cnt = a.numel() // self._cw()
         _lib.check(self.lib.fthe_sub_dev(self._key, self.dev.ctx, ctypes.c_void_p(a.data_ptr()),

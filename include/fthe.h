@@ -91,6 +91,24 @@ void  fthe_host_free(void *p);
  * fthe_key_from_primes   same derivation from caller primes (injected keys).
  * fthe_key_from_n        public key only: Paillier::operator=, paillier.h:12-18
  *                        (copies modulus/generator/keyLength only).
+ *
+ * Paillier-3072.  An odd n of 96 words (3041..3072 bits; n^2 of 6081..6144 bits, rows of 192 words) has no
+ * op-program kernel mod n^2 (fthe_kernel_limbs(6144) is 0), but its keys are accepted: the product of rows mod
+ * n^2 runs on a kernel of its own (fthe_mul192, fedtree_amd/csrc/fthe_mul192.hip), and with it
+ *     fthe_add[_dev], fthe_reduce_kway[_dev] (k of 1..64; k = 1 reduces its rows),
+ *     fthe_scalar_mul_u64[_dev], fthe_scalar_mul_words[_dev]
+ * on any rows of 192 words (rows >= n^2 included), results in [0, n^2); out may alias as for the other sizes, and
+ * the _dev forms want their row arrays 16-byte aligned (the kernel moves rows in 16-byte pieces; any hipMalloc'd
+ * or torch buffer, and any whole-row offset into one, is).  fthe_reduce_kway_dev with an out that overlaps a plane
+ * other than exactly plane 0 or 1, and the scalar muls with e > 0, keep count x 768 B in the context's scratch,
+ * under fthe_ctx_set_mem_limit (FTHE_ERR_NOMEM above it).  The host add is staged in chunks of 65,536 rows
+ * (FTHE_MUL192_CHUNK overrides, read per call).  fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.  Every other call that works
+ * mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits, fthe_invert, fthe_sub_inv,
+ * fthe_scalar_mul_rows, fthe_dot_segments, fthe_reduce_segments, fthe_scan_segments, the histogram calls, the
+ * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the packed and slot-packed pair
+ * calls, the public-key encrypt, and fthe_add_shared / fthe_scalar_mul_u64_shared.  A key holder's CRT encrypt
+ * and decrypt at this size run mod p^2, q^2 as before; they are not part of this paragraph's claim.
+ * n of 2049..3040 bits stays FTHE_ERR_UNSUPPORTED.
  */
 int  fthe_key_generate(fthe_ctx *ctx, int n_bits, uint64_t seed, fthe_key **out);
 /* fthe_key_generate_ex   flags 0: fthe_key_generate.  FTHE_KEYGEN_KNOWN_ORDER: p and q
@@ -637,6 +655,10 @@ int fthe_debug_direct_y(fthe_key *key, fthe_ctx *ctx, uint64_t rng_seed, uint64_
  * out == NULL: only *len.  FTHE_ERR_UNSUPPORTED unless n^2 has 4095-4096 bits.
  * Host only (tests compare it with tools/addb_model.py addb_image). */
 int fthe_debug_addb_image(const uint32_t *n, int n_words, uint8_t *out, size_t cap, size_t *len);
+/* The per-key context of fthe_mul192 (mu and N as 232 limbs of 27 bits, N as 192 dwords), built on the host from n
+ * exactly as at key set-up; out == NULL: only *len.  FTHE_ERR_UNSUPPORTED unless n is odd with 3041..3072 bits.
+ * Host only (tests compare it with tools/mul192_model.py image). */
+int fthe_debug_mul192_image(const uint32_t *n, int n_words, uint8_t *out, size_t cap, size_t *len);
 /* The per-key context of fthe_nadic_b76, the parties' public-key encrypt on base-n digits with matrix-core
  * Barrett reductions (party.h:118-142 -> paillier.cpp:122-139): mu and n copies, column corrections, n's 27-bit
  * limbs, built on the host from n exactly as at key set-up; out == NULL: only *len.  FTHE_ERR_UNSUPPORTED

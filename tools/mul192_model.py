@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Bit-exact model of the Paillier-3072 ciphertext product (fthe_mul192, fedtree_amd/csrc/fthe_mul192.hip).
+
+out = x y mod N for N = n^2, n odd with 96 words (3041..3072 bits, so 2^6080 <= N < 2^6144), x and y any rows
+of 192 dwords (below 2^6144, rows >= N included).  Limbs have B = 27 bits; an operand has 232 of them (8 lanes
+x 29), a product 464 columns.
+
+Product (ring()).  Lane l of the octet owns limbs [29 l, 29 l + 29).  Step s adds x_limb * m[s] into the lane's
+ring of 29 columns (lane l: columns 29 l + s .. 29 l + s + 28); the lowest column then moves one lane down, lane
+7 takes 0, lane 0's retires through a carry chain as limb s.  A column receives at most 232 products below
+2^54, so every 64-bit accumulator stays below 2^62 (asserted), carry included.
+
+Barrett.  With a = 27 * 225 = 6075 and b = 27 * 231 = 6237:
+    z1 = floor(z / 2^a) < 2^(12288 - 6075) = 2^6213             231 limbs
+    mu = floor(2^(a + b) / N) <= 2^(12312 - 6080) = 2^6232       231 limbs
+    q  = floor(z1 mu / 2^b) < 2^6208                             230 limbs
+z1 mu / 2^b <= z / N, and z1 > z / 2^a - 1, mu > 2^(a+b) / N - 1 give
+    z1 mu / 2^b > z / N - z / 2^(a+b) - 2^a / N > z / N - 2^-24 - 2^-5,
+so q is floor(z / N) or one below it and r = z - q N lies in [0, 2N): one conditional subtraction.  The
+kernel forms r modulo 2^(27 * 228) (2N < 2^6145), limb by limb in the borrow chain of z - q N.  r may reach
+2^6144, one bit more than a row: the subtraction runs on the row's 192 dwords, and is taken when it leaves no
+borrow or when that bit (limb 227, bit 15) is set.
+
+Run:  python tools/mul192_model.py [seed] [trials]
+"""
+import random
+import sys
+
+import numpy as np
+
+B = 27
+MASK = (1 << B) - 1
+LANES, PER = 8, 29
+LIMBS = LANES * PER                 # 232
+WORDS = 192
+SHIFT_A, SHIFT_B = 225, 231         # limbs
+R_LIMBS = 228
+
+
+def edge_moduli(seed=3072):
+    """odd n at the edges of the range: the largest and the smallest N, a 3071-bit n, N just below and just above
+    2^6143, and a seeded random 3072-bit n (none needs to be a semiprime)"""
+    from math import isqrt
+    s = isqrt(1 << 6143)
+    lo = s - (1 - s % 2)
+    assert lo * lo < 1 << 6143 < (lo + 2) ** 2
+    return [(1 << 3072) - 1, (1 << 3040) + 1, (1 << 3071) - 1, lo, lo + 2,
+            random.Random(seed).getrandbits(3072) | (1 << 3071) | 1]
+
+
+def n_ok(n):
+    return n % 2 == 1 and 3041 <= n.bit_length() <= 3072
+
+
+def limbs(v, count=LIMBS):
+    assert 0 <= v < 1 << (B * count)
+    return [(v >> (B * j)) & MASK for j in range(count)]
+
+
+def value(ls):
+    return sum(int(x) << (B * j) for j, x in enumerate(ls))
+
+
+def mu_of(N):
+    return (1 << (B * (SHIFT_A + SHIFT_B))) // N
+
+
+def image(n):
+    """the kernel's per-key context bytes (mul192_image.hpp): mu limbs, N limbs, N dwords"""
+    assert n_ok(n)
+    N = n * n
+    mu = mu_of(N)
+    assert mu < 1 << (B * SHIFT_B)
+    words = limbs(mu) + limbs(N) + [(N >> (32 * j)) & 0xFFFFFFFF for j in range(WORDS)]
+    return np.array(words, dtype="<u4").tobytes()
+
+
+def ring(xl, ml, drain=True):
+    """the limbs of value(xl) * value(ml) as the octet forms them: 232 (drain: 464) of them"""
+    x = np.array(xl, dtype=np.uint64).reshape(LANES, PER)
+    acc = np.zeros((LANES, PER), dtype=np.uint64)
+    out, carry, peak = [], 0, 0
+    for s in range(2 * LIMBS if drain else LIMBS):
+        t = s % PER
+        if s < LIMBS:
+            acc[:, (t + np.arange(PER)) % PER] += x * np.uint64(ml[s])
+            peak = max(peak, int(acc.max()))
+        carry += int(acc[0, t])
+        peak = max(peak, carry)
+        out.append(carry & MASK)
+        carry >>= B
+        acc[:-1, t] = acc[1:, t]
+        acc[-1, t] = 0
+    assert peak < 1 << 62, "64-bit column overflow"
+    assert not drain or (carry == 0 and not acc.any())
+    return out
+
+
+def mul(x, y, n, lanes=False):
+    """x y mod n^2 step by step; lanes: the three products through ring() (slow), else by Python integers"""
+    assert n_ok(n) and 0 <= x < 1 << (32 * WORDS) and 0 <= y < 1 << (32 * WORDS)
+    N = n * n
+    mu = mu_of(N)
+    assert 1 << 6080 <= N < 1 << 6144 and mu < 1 << (B * SHIFT_B)
+    prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
+    z = prod(x, y)
+    assert z == x * y and z < 1 << (B * (SHIFT_A + SHIFT_B))
+    z1 = z >> (B * SHIFT_A)
+    assert z1 < 1 << (B * SHIFT_B)                       # fits the operand registers (232 limbs)
+    q = prod(z1, mu) >> (B * SHIFT_B)
+    assert q < 1 << (B * 230) and z // N - 1 <= q <= z // N
+    if lanes:
+        t = ring(limbs(q), limbs(N), drain=False)        # the low 232 limbs of q N
+        zl, rl, borrow = limbs(z, 2 * LIMBS), [], 0
+        for s in range(LIMBS):
+            d = (zl[s] - t[s] - borrow) & 0xFFFFFFFF
+            borrow = d >> 31
+            rl.append(d & MASK if s < R_LIMBS else 0)
+        r = value(rl)
+    else:
+        r = (z - q * N) % (1 << (B * R_LIMBS))
+    assert r == z - q * N and 0 <= r < 2 * N
+    # the row holds r mod 2^6144; r >= N when the subtraction leaves no borrow or r has a bit above the row
+    row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
+    assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
+    if high or row >= N:
+        row = (row - N) % (1 << (32 * WORDS))
+    r = row
+    assert r == x * y % N
+    return r
+
+
+def main():
+    seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+    trials = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    rng = random.Random(seed)
+    top = (1 << (32 * WORDS)) - 1
+    for n in edge_moduli(seed):
+        assert mul(top, top, n, lanes=True) == top * top % (n * n)
+        for _ in range(trials):
+            x, y = rng.getrandbits(32 * WORDS), rng.getrandbits(32 * WORDS)
+            mul(x, y, n, lanes=trials <= 4)
+    print("mul192 model: ok")
+
+
+if __name__ == "__main__":
+    main()
