@@ -3644,13 +3644,15 @@ static int launch_mul192(fthe_ctx *c, const fthe_key *k, const uint32_t *x, cons
 // A call on fthe_mul192 has no slots: begin_call's device check, then (the context's device being current, as for
 // every allocation of a call) scratch bytes of c->scratch under the cap of fthe_ctx_set_mem_limit, as begin_call
 // holds the slot region under it, then the time mark; end_call's accounting.
+static int mul192_scratch(fthe_ctx *c, size_t bytes) {
+    if (c->mem_limit && bytes > c->mem_limit && bytes > c->scratch.n) return FTHE_ERR_NOMEM;
+    return c->scratch.ensure(bytes);
+}
 static int mul192_begin(fthe_ctx *c, const fthe_key *k, size_t scratch = 0) {
     if (k->device != c->device) return FTHE_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
-    if (scratch) {
-        if (c->mem_limit && scratch > c->mem_limit && scratch > c->scratch.n) return FTHE_ERR_NOMEM;
-        if (int rc = c->scratch.ensure(scratch)) return rc;
-    }
+    if (scratch)
+        if (int rc = mul192_scratch(c, scratch)) return rc;
     return mark_start(c);
 }
 // rows per chunk of a host-resident add: the row-I/O add's footprint per chunk; FTHE_MUL192_CHUNK overrides (read
@@ -4291,12 +4293,16 @@ extern "C" int fthe_sub_inv_dev(fthe_key *k, fthe_ctx *c, const uint32_t *a, con
 // the building block of the segmented product and the segmented scan.  One
 // launch per chunk: K gathered tile loads, then X = x_0; X <- x_j X R^-1;
 // X <- X (R^K) R^-1.  idx is a host array, uploaded per pass.
+// Paillier-3072 (d_mul192): no op-program and no slots, one launch of fthe_gprod192 per pass.  Its
+// dst must not overlap src, so a pass whose ranges overlap runs into c->scratch, behind the room of a pass's
+// indices, under fthe_ctx_set_mem_limit, and is copied out.
 namespace {
 struct GatherProd {
     fthe_key *k; fthe_ctx *c;
     static constexpr int K = 8;
     Launch Lc; int base = 0; double mm = 0; size_t prog_words = 0;
     int init(size_t maxG) {
+        if (k->d_mul192) return mul192_begin(c, k);
         base = nslots_for(k);
         int rc = begin_call(c, k, maxG, Lc, base + K, k->sn2);
         if (rc) return rc;
@@ -4329,9 +4335,27 @@ struct GatherProd {
         return FTHE_OK;
     }
     // idx: K x G host indices into src (rows of cw words; src holds src_rows rows)
+    static size_t idx_room(size_t G) { return ((size_t)K * G * 8 + 255) / 256 * 256; }
+    bool disjoint(const uint32_t *src, size_t src_rows, size_t G, const uint32_t *dst) const {
+        const size_t rb = 2 * (size_t)k->n_words * 4;
+        const char *d0 = (const char *)dst, *s0 = (const char *)src;
+        return d0 + G * rb <= s0 || s0 + src_rows * rb <= d0;
+    }
+    // Where a pass of fthe_gprod192 writes: dst, or, where dst overlaps src, c->scratch behind the room of the pass's
+    // index lists (under fthe_ctx_set_mem_limit).  The one place that knows this layout: run() calls it before it
+    // uploads idx to the front of c->scratch, so that run_dev's call finds the buffer sized and moves nothing.
+    int gather_dest(const uint32_t *src, size_t src_rows, size_t G, uint32_t *dst, uint32_t **to) {
+        *to = dst;
+        if (disjoint(src, src_rows, G, dst)) return FTHE_OK;
+        if (int rc = mul192_scratch(c, idx_room(G) + G * mul192::kWords * 4)) return rc;
+        *to = (uint32_t *)((char *)c->scratch.p + idx_room(G));
+        return FTHE_OK;
+    }
     int run(const uint32_t *src, size_t src_rows, const std::vector<int64_t> &idx, size_t G, uint32_t *dst) {
         int rc;
         HIPOK(hipStreamSynchronize(c->stream));          // previous pass done with scratch
+        uint32_t *to;                                    // sizes scratch for the pass's rows too, before idx goes there
+        if (k->d_mul192 && (rc = gather_dest(src, src_rows, G, dst, &to))) return rc;
         if ((rc = c->scratch.ensure(std::max<size_t>(8, idx.size() * 8)))) return rc;
         if (!idx.empty()) HIPOK(hipMemcpy(c->scratch.p, idx.data(), idx.size() * 8, hipMemcpyHostToDevice));
         return run_dev(src, src_rows, (const int64_t *)c->scratch.p, G, dst);
@@ -4341,9 +4365,15 @@ struct GatherProd {
         const int cw = 2 * k->n_words, S = Lc.S, L = Lc.L;
         int rc;
         // the chain of launches re-reads src after the first one has written dst: only for disjoint ranges
-        const size_t rb = (size_t)cw * 4;
-        const char *d0 = (const char *)dst, *s0 = (const char *)src;
-        const bool disjoint = d0 + G * rb <= s0 || s0 + src_rows * rb <= d0;
+        const bool disjoint = this->disjoint(src, src_rows, G, dst);
+        if (k->d_mul192) {
+            uint32_t *to;
+            if ((rc = gather_dest(src, src_rows, G, dst, &to))) return rc;
+            if (mul192::launch_gather(c->stream, src, gidx, to, k->d_mul192, G, c->n_cu) != hipSuccess) return FTHE_ERR_HIP;
+            if (to != dst) HIPOK(hipMemcpyAsync(dst, to, G * (size_t)cw * 4, hipMemcpyDeviceToDevice, c->stream));
+            Lc.mm += (double)G * (K - 1);
+            return FTHE_OK;
+        }
         if (k->d_addb && c->fn_addb && disjoint) {
             // 2048-bit n: K - 1 matrix-core Barrett add launches over all G rows, gathered operands
             // (dst = src[i_0] src[i_1], then dst = dst src[i_j]; an index < 0 is the integer 1)
@@ -4384,7 +4414,7 @@ struct GatherProd {
 extern "C" int fthe_reduce_segments_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count,
                                         const int64_t *seg_ptr, const int64_t *idx, size_t nseg, uint32_t *out) {
     if (!k || !c || !seg_ptr || (nseg && !out)) return FTHE_ERR_ARG;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     if (seg_ptr[0] != 0) return FTHE_ERR_ARG;
     for (size_t s = 0; s < nseg; s++) if (seg_ptr[s + 1] < seg_ptr[s]) return FTHE_ERR_ARG;
     size_t total = (size_t)seg_ptr[nseg];
@@ -4491,6 +4521,10 @@ static int fold_zero_first(fthe_key *k, fthe_ctx *c, const int64_t *seg_dev, siz
     if ((rc = c->ezm.ensure(nseg * (size_t)cw * 4))) return rc;
     hipLaunchKernelGGL(k_zero_first_rows, dim3((unsigned)((nseg * cw + 255) / 256)), dim3(256), 0, c->stream,
                        enc_zero, seg_dev, nseg, cw, (uint32_t *)c->ezm.p);
+    if (k->d_mul192) {
+        if ((rc = mul192_begin(c, k)) || (rc = launch_mul192(c, k, out, (const uint32_t *)c->ezm.p, out, nseg))) return rc;
+        return mul192_end(c, (double)nseg);
+    }
     const uint32_t *xs[2] = {out, (const uint32_t *)c->ezm.p};
     Mpz R2; mpz_powm_ui(R2, k->mn2.m.R, 2ul, k->n2);
     return rowprod_impl(k, c, xs, 2, nseg, out, R2, true);    // row-wise, alias-safe
@@ -4499,7 +4533,7 @@ static int fold_zero_first(fthe_key *k, fthe_ctx *c, const int64_t *seg_dev, siz
 extern "C" int fthe_reduce_segments_csr_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t count,
                                             const int64_t *seg_ptr, const int64_t *idx, size_t nseg, uint32_t *out) {
     if (!k || !c || !seg_ptr || (nseg && !out)) return FTHE_ERR_ARG;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     if (!nseg) return FTHE_OK;
     HIPOK(hipSetDevice(c->device));
     int64_t ends[1] = {0};
@@ -4520,7 +4554,7 @@ static int histogram_impl(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t co
                           const uint8_t *bin_ids, int n_col, const int32_t *cut_col_ptr, int max_num_bin,
                           const int32_t *inst, size_t n_sel, const uint32_t *enc_zero, uint32_t *out) {
     if (!k || !c || !cut_col_ptr || n_col <= 0 || planes <= 0 || (!inst && n_sel > count)) return FTHE_ERR_ARG;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     if (cut_col_ptr[0] != 0) return FTHE_ERR_ARG;
     for (int f = 0; f < n_col; f++) if (cut_col_ptr[f + 1] < cut_col_ptr[f]) return FTHE_ERR_ARG;
     const int64_t n_bins = cut_col_ptr[n_col];
@@ -4586,7 +4620,7 @@ extern "C" int fthe_histogram_zero_first_dev(fthe_key *k, fthe_ctx *c, const uin
 extern "C" int fthe_scan_segments_dev(fthe_key *k, fthe_ctx *c, const uint32_t *x, const int64_t *seg_ptr,
                                       size_t nseg, uint32_t *out) {
     if (!k || !c || !seg_ptr) return FTHE_ERR_ARG;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     if (seg_ptr[0] != 0) return FTHE_ERR_ARG;
     size_t longest = 0;
     for (size_t s = 0; s < nseg; s++) {

@@ -17,6 +17,9 @@
 //      product retires its limbs straight into the borrow chain of z - q N.
 //   4. r -> dwords (lane l: dwords [24 l, 24 l + 24); r < 2N may have bit 6144 set, which stays in its limb), one
 //      conditional subtraction of N mod 2^6144 with the borrow resolved across the octet, rows stored.  Every operand row of a batch is loaded before any is stored.
+//
+// fthe_gprod192, below it, is the gathered 8-way product on the same routines: steps 2 and 3 per member with the
+// remainder kept in LDS as the next multiplier, steps 1 and 4 once per group.
 #include <algorithm>
 #include <utility>
 
@@ -145,6 +148,59 @@ __device__ inline void load_row(const uint32_t *base, uint64_t row, int l, uint4
     }
 }
 
+// Step 3: z as 464 limbs in area -> r = z - q N in [0, 2N) as limbs in area[0, 228), limbs 228 .. 231 zero: the
+// form of a multiplier column.  xl is scratch.
+__device__ inline void barrett(uint32_t (&xl)[kPerLane], uint32_t *area, const uint32_t *s_mu, const uint32_t *s_nl, int l,
+                               bool lane0, bool top) {
+    wave_sync();
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftA + kPerLane * l + i];
+    wave_sync();
+    product<kHigh>(xl, s_mu, area, lane0, top);                     // (z >> 27*225) mu
+    wave_sync();
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftB + kPerLane * l + i];
+    wave_sync();
+    product<kSub>(xl, s_nl, area, lane0, top);                      // r = z - q N
+    wave_sync();
+}
+
+// Step 4: r in [0, 2N) as limbs in area[0, 228) -> the lane's 24 dwords of r mod N (lane l: dwords [24 l, 24 l + 24))
+__device__ inline void canonical_dwords(const uint32_t *area, const uint32_t *s_nd, int l, bool lane0, uint32_t (&r)[24]) {
+    const int lo = opaque(l);
+    const uint32_t *nd = s_nd + 24 * lo;
+#pragma unroll
+    for (int k = 0; k < 24; k++) {
+        const uint32_t bit = 32u * (uint32_t)(24 * lo + k), j = bit / kLimbBits;
+        const uint64_t v = (uint64_t)area[j] | (uint64_t)area[j + 1] << 27 | (uint64_t)area[j + 2] << 54;
+        r[k] = (uint32_t)(v >> (bit - kLimbBits * j));
+    }
+    // r - N: the lane's own borrow g, and whether a borrow from below passes through (the difference is 0)
+    uint32_t g = 0, any = 0;
+#pragma unroll
+    for (int k = 0; k < 24; k++) {
+        const uint64_t d = (uint64_t)r[k] - nd[k] - g;
+        g = (uint32_t)(d >> 63);
+        any |= (uint32_t)d;
+    }
+    const uint32_t pass = any == 0 ? 1u : 0u;
+    uint32_t bin = 0, bout = g;
+#pragma unroll
+    for (int it = 0; it < kLanes - 1; it++) {
+        const uint32_t up = __shfl_up(bout, 1, kLanes);
+        bin = lane0 ? 0u : up;
+        bout = g | (bin & pass);
+    }
+    // r < N: the octet's last borrow, unless r has bits above the row (r < 2N may reach 2^6144: limb 227, bit 15)
+    const bool keep = __shfl(bout, kLanes - 1, kLanes) != 0 && (area[kRLimbs - 1] >> (32 * kWords % kLimbBits)) == 0;
+#pragma unroll
+    for (int k = 0; k < 24; k++) {
+        const uint64_t d = (uint64_t)r[k] - nd[k] - bin;
+        bin = (uint32_t)(d >> 63);
+        r[k] = keep ? r[k] : (uint32_t)d;
+    }
+}
+
 __global__ __launch_bounds__(64 * kWaves) void fthe_mul192_kernel(const uint32_t *x, const uint32_t *y, uint32_t *out,
                                                                   const uint32_t *kctx, uint32_t count, uint32_t nwg) {
     __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
@@ -185,50 +241,9 @@ __global__ __launch_bounds__(64 * kWaves) void fthe_mul192_kernel(const uint32_t
         limbs_of(area, l, xl);
         wave_sync();
         product<kFull>(xl, area, area, lane0, top);                     // z
-        wave_sync();
-#pragma unroll
-        for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftA + kPerLane * l + i];
-        wave_sync();
-        product<kHigh>(xl, s_mu, area, lane0, top);                     // (z >> 27*225) mu
-        wave_sync();
-#pragma unroll
-        for (int i = 0; i < kPerLane; i++) xl[i] = area[kShiftB + kPerLane * l + i];
-        wave_sync();
-        product<kSub>(xl, s_nl, area, lane0, top);                      // r = z - q N
-        wave_sync();
+        barrett(xl, area, s_mu, s_nl, l, lane0, top);
         uint32_t r[24];
-        const int lo = opaque(l);
-        const uint32_t *nd = s_nd + 24 * lo;
-#pragma unroll
-        for (int k = 0; k < 24; k++) {
-            const uint32_t bit = 32u * (uint32_t)(24 * lo + k), j = bit / kLimbBits;
-            const uint64_t v = (uint64_t)area[j] | (uint64_t)area[j + 1] << 27 | (uint64_t)area[j + 2] << 54;
-            r[k] = (uint32_t)(v >> (bit - kLimbBits * j));
-        }
-        // r - N: the lane's own borrow g, and whether a borrow from below passes through (the difference is 0)
-        uint32_t g = 0, any = 0;
-#pragma unroll
-        for (int k = 0; k < 24; k++) {
-            const uint64_t d = (uint64_t)r[k] - nd[k] - g;
-            g = (uint32_t)(d >> 63);
-            any |= (uint32_t)d;
-        }
-        const uint32_t pass = any == 0 ? 1u : 0u;
-        uint32_t bin = 0, bout = g;
-#pragma unroll
-        for (int it = 0; it < kLanes - 1; it++) {
-            const uint32_t up = __shfl_up(bout, 1, kLanes);
-            bin = lane0 ? 0u : up;
-            bout = g | (bin & pass);
-        }
-        // r < N: the octet's last borrow, unless r has bits above the row (r < 2N may reach 2^6144: limb 227, bit 15)
-        const bool keep = __shfl(bout, kLanes - 1, kLanes) != 0 && (area[kRLimbs - 1] >> (32 * kWords % kLimbBits)) == 0;
-#pragma unroll
-        for (int k = 0; k < 24; k++) {
-            const uint64_t d = (uint64_t)r[k] - nd[k] - bin;
-            bin = (uint32_t)(d >> 63);
-            r[k] = keep ? r[k] : (uint32_t)d;
-        }
+        canonical_dwords(area, s_nd, l, lane0, r);
         if (live) {
             uint4 *p = (uint4 *)(out + row * kWords + 24 * l);
 #pragma unroll
@@ -238,7 +253,94 @@ __global__ __launch_bounds__(64 * kWaves) void fthe_mul192_kernel(const uint32_t
     }
 }
 
+// fthe_gprod192: out[g] = prod_{j < 8} src[gidx[j G + g]] mod N (an index below 0: the integer 1), the gathered
+// product behind the segmented products, the histogram and the segmented scan.  The geometry above;
+// an octet owns group g and walks its members with the running product resident in LDS:
+//
+//   member 0 -> staging words -> limbs -> the octet's multiplier column area[0, 232);
+//   step j = 1 ..: member j -> staging words -> limbs x in registers, z = x r (kFull, the multiplier column being r),
+//   then step 3 above, which leaves r in [0, 2N) where the next step's multiplier column is read: no dwords, no
+//   conditional subtraction, no store and no reload between members.  r < 2N <= 2^6145 makes z < 2^12289, one bit
+//   above a product of two rows; the cut points hold for it (tools/mul192_model.py chain()).
+//   After the last step only: step 4 and the store.
+//
+// The product routine is wave-wide, so a wave runs max(2, members of its longest group) - 1 steps; an octet without
+// a member j multiplies by 1 there.  At least one step: a lone member >= N comes out reduced, no member gives 1.
+// Lane j of an octet holds the group's index j (K = 8 = the lanes of an octet) until the steps are counted; each
+// step then reads its index again, which keeps two registers free across the products.  Every member of a wave's
+// batch is read before the batch stores; across batches dst must not overlap src.
+constexpr int kGather = kLanes;
+
+__global__ __launch_bounds__(64 * kWaves) void fthe_gprod192_kernel(const uint32_t *src, const int64_t *gidx, uint32_t *dst,
+                                                                    const uint32_t *kctx, uint64_t count, uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint64_t nbatch = (count + kRowsPerWave - 1) / kRowsPerWave;
+    for (;;) {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&s_next, 1u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        const uint64_t batch = blockIdx.x + (uint64_t)t * nwg;
+        if (batch >= nbatch) break;
+        const uint64_t g = batch * kRowsPerWave + oct;
+        const bool live = g < count;           // an idle octet has no member: it multiplies 1 by 1 and stores nothing
+        // the wave's step count: one more than the highest member position that any of its octets fills
+        const int64_t mine = live ? gidx[(uint64_t)l * count + g] : -1;
+        const uint64_t has = __ballot(mine >= 0);
+        uint32_t pos = (uint32_t)has | (uint32_t)(has >> 32);
+        pos |= pos >> 16;
+        pos = (pos | pos >> 8) & 0xffu;
+        const int members = __builtin_amdgcn_readfirstlane(32 - __builtin_clz(pos | 1u));
+        uint4 v[6];
+        uint32_t xl[kPerLane];
+        int64_t at = __shfl(mine, 0, kLanes);
+        load_row(at >= 0 ? src : nullptr, (uint64_t)at, l, v);
+        stage(area, v, l);
+        wave_sync();
+        limbs_of(area, l, xl);
+#pragma unroll
+        for (int i = 0; i < kPerLane; i++) area[kPerLane * l + i] = xl[i];
+        wave_sync();
+#pragma unroll 1
+        for (int j = 1; j < (members < 2 ? 2 : members); j++) {
+            at = live ? gidx[(uint64_t)j * count + g] : -1;
+            load_row(at >= 0 ? src : nullptr, (uint64_t)at, l, v);
+            stage(area, v, l);                 // over the spent high limbs of the step before
+            wave_sync();
+            limbs_of(area, l, xl);
+            wave_sync();
+            product<kFull>(xl, area, area, lane0, top);                 // z = x r
+            barrett(xl, area, s_mu, s_nl, l, lane0, top);
+        }
+        uint32_t r[24];
+        canonical_dwords(area, s_nd, l, lane0, r);
+        if (live) {
+            uint4 *p = (uint4 *)(dst + g * kWords + 24 * l);
+#pragma unroll
+            for (int k = 0; k < 6; k++) p[k] = make_uint4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+        }
+        wave_sync();
+    }
+}
+
 }  // namespace
+
+int launch_gather(hipStream_t st, const uint32_t *src, const int64_t *gidx, uint32_t *dst, const void *kctx, size_t count,
+                  int n_cu) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<size_t>((count + kPerWg - 1) / kPerWg, (size_t)std::max(n_cu, 1));
+    hipLaunchKernelGGL(fthe_gprod192_kernel, dim3(blocks), dim3(64 * kWaves), 0, st, src, gidx, dst, (const uint32_t *)kctx,
+                       (uint64_t)count, blocks);
+    return hipGetLastError();
+}
 
 int launch(hipStream_t st, const uint32_t *x, const uint32_t *y, uint32_t *out, const void *kctx, size_t count, int n_cu) {
     if (count == 0) return hipSuccess;

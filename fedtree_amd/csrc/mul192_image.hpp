@@ -55,4 +55,10 @@ inline bool build(const mpz_t n, std::vector<uint8_t> &img) {
 // out may be exactly x or y.  kctx: the device copy of build()'s bytes.  Returns a hipError_t.
 int launch(hipStream_t st, const uint32_t *x, const uint32_t *y, uint32_t *out, const void *kctx, size_t count, int n_cu);
 
+// dst[g] = prod_{j < 8} src[gidx[j count + g]] mod N for count groups on fthe_gprod192 (one launch; rows and indices
+// are addressed in 64 bits); gidx: 8 lists of count device indices into src, one below 0 standing for the integer 1
+// (a group of none gives 1, a group of one its row reduced).  dst must not overlap src.  Returns a hipError_t.
+int launch_gather(hipStream_t st, const uint32_t *src, const int64_t *gidx, uint32_t *dst, const void *kctx, size_t count,
+                  int n_cu);
+
 }  // namespace mul192

@@ -102,9 +102,14 @@ void  fthe_host_free(void *p);
  * or torch buffer, and any whole-row offset into one, is).  fthe_reduce_kway_dev with an out that overlaps a plane
  * other than exactly plane 0 or 1, and the scalar muls with e > 0, keep count x 768 B in the context's scratch,
  * under fthe_ctx_set_mem_limit (FTHE_ERR_NOMEM above it).  The host add is staged in chunks of 65,536 rows
- * (FTHE_MUL192_CHUNK overrides, read per call).  fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.  Every other call that works
- * mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits, fthe_invert, fthe_sub_inv,
- * fthe_scalar_mul_rows, fthe_dot_segments, fthe_reduce_segments, fthe_scan_segments, the histogram calls, the
+ * (FTHE_MUL192_CHUNK overrides, read per call).  The gathered 8-way product of such rows runs on a second kernel of
+ * that file (fthe_gprod192: the running product stays in LDS between a group's members), and with it
+ *     fthe_reduce_segments[_dev], fthe_reduce_segments_csr_dev, fthe_reduce_segments_zero_first_dev,
+ *     fthe_histogram_dev, fthe_histogram_zero_first_dev, fthe_scan_segments[_dev]
+ * with the same rows in and out; a pass whose out overlaps its source rows keeps that pass's rows in the context's
+ * scratch, under the same limit.  fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.
+ * Every other call that works mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits,
+ * fthe_invert, fthe_sub_inv, fthe_scalar_mul_rows, fthe_dot_segments, the
  * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the packed and slot-packed pair
  * calls, the public-key encrypt, and fthe_add_shared / fthe_scalar_mul_u64_shared.  A key holder's CRT encrypt
  * and decrypt at this size run mod p^2, q^2 as before; they are not part of this paragraph's claim.

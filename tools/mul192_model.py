@@ -130,6 +130,55 @@ def mul(x, y, n, lanes=False):
     return r
 
 
+def chain(rows, n, lanes=False):
+    """prod(rows) mod n^2 as fthe_gprod192 forms it: the first row is the multiplier column, every
+    further row x gives z = x r and the lazy remainder r = z - q N in [0, 2N), which stays in limbs as the next
+    multiplier; only the last r is made canonical.  Fewer than two rows are filled up with the integer 1, so there is
+    always one product.  The multiplier is now below 2N <= 2^6145, not below 2^6144:
+        z  = x r              < 2^(6144 + 6145) = 2^12289
+        z1 = floor(z / 2^a)   < 2^6214                     231 limbs (below 2^6237)
+        q  = floor(z1 mu/2^b) <= z / N < 2^6209            230 limbs (below 2^6210)
+        z1 mu / 2^b > z / N - z / 2^(a+b) - 2^a / N > z / N - 2^-23 - 2^-5
+    so q is still floor(z / N) or one below it, and r < 2N < 2^(27 * 228) with limbs 228..231 zero.  Every bound is
+    asserted.  lanes: the three products of every step through ring() (slow)."""
+    assert n_ok(n) and all(0 <= x < 1 << (32 * WORDS) for x in rows)
+    N = n * n
+    mu = mu_of(N)
+    prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
+    rows = list(rows) + [1] * (2 - len(rows))
+    r = rows[0]
+    for x in rows[1:]:
+        assert r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
+        z = prod(x, r)
+        assert z == x * r and z < 1 << 12289
+        z1 = z >> (B * SHIFT_A)
+        assert z1 < 1 << 6214 < 1 << (B * SHIFT_B)
+        t = prod(z1, mu)
+        assert t < 1 << (B * 2 * LIMBS)                      # the 464 limbs the drain retires
+        q = t >> (B * SHIFT_B)
+        assert q < 1 << 6209 < 1 << (B * 230) and z // N - 1 <= q <= z // N
+        if lanes:
+            low = ring(limbs(q), limbs(N), drain=False)
+            zl, rl, borrow = limbs(z, 2 * LIMBS), [], 0
+            for s in range(LIMBS):
+                d = (zl[s] - low[s] - borrow) & 0xFFFFFFFF
+                borrow = d >> 31
+                rl.append(d & MASK if s < R_LIMBS else 0)
+            r = value(rl)
+        else:
+            r = (z - q * N) % (1 << (B * R_LIMBS))
+        assert r == z - q * N and 0 <= r < 2 * N
+    row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
+    assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
+    if high or row >= N:
+        row = (row - N) % (1 << (32 * WORDS))
+    want = 1
+    for x in rows:
+        want = want * x % N
+    assert row == want
+    return row
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -140,6 +189,7 @@ def main():
         for _ in range(trials):
             x, y = rng.getrandbits(32 * WORDS), rng.getrandbits(32 * WORDS)
             mul(x, y, n, lanes=trials <= 4)
+        chain([top] * 3 + [rng.getrandbits(32 * WORDS) for _ in range(5)], n, lanes=trials <= 4)
     print("mul192 model: ok")
 
 
