@@ -478,7 +478,8 @@ struct fthe_key {
     bool add_classical = false;               // pr_add_w is one classical product (no R^2 constant)
     void *d_addb = nullptr;                   // fthe_addb_q152's per-key context (addb_image.hpp): n of 2048 bits
     // fthe_mul192's per-key context (mul192_image.hpp): n of 96 words.  Such a key has no op-program kernel mod n^2
-    // (pub_ok stays false): add, k-way product and the uniform scalar mul run on fthe_mul192, nothing else does
+    // (pub_ok stays false): add and k-way product run on fthe_mul192, the gathered products on fthe_gprod192, the
+    // uniform scalar mul and the public-key encrypt on fthe_pow192; nothing else works mod n^2
     void *d_mul192 = nullptr;
     PH pr_enc_pub, pr_add, pr_sub, pr_enc_p, pr_enc_q, pr_enc_p_nt, pr_enc_tail, pr_dec_pl, pr_dec_ql, pr_enc_pl, pr_enc_ql, pr_dec_p, pr_dec_q, pr_dec_hp, pr_dec_hq, pr_dec_t;
     PH pr_encA_p, pr_encA_q;      // stage A of the CRT encrypt (mod p, q; small kernel)
@@ -2088,6 +2089,8 @@ static int encrypt_xb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, con
                            int y_words, uint64_t rng_seed, uint32_t *out, HostPipe *pipe);
 static int encrypt_pb_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const uint32_t *y, int y_words,
                            uint64_t rng_seed, uint32_t *out, HostPipe *pipe);
+static int encrypt_pow192(fthe_key *k, fthe_ctx *c, const MsgSrc &m, size_t count, const uint32_t *r, int r_words,
+                          uint64_t rng_seed, uint32_t *out, HostPipe *pipe);
 // One chunk of the direct-y CRT encrypt: y_p, y_q drawn into scratch, the two stage-B exponentiations in the
 // plan's form, the recombination into out.
 static int enc_direct_y_chunk(CallPlan &pl, const MsgSrc &m, const RngKey &rk, size_t off, size_t cnt, uint32_t *out) {
@@ -2157,6 +2160,8 @@ static int encrypt_impl(fthe_key *k, fthe_ctx *c, MsgSrc m, size_t count, const 
         if (!pb_ready) return k->priv ? FTHE_ERR_UNSUPPORTED : FTHE_ERR_NOPRIV;
         return encrypt_pb_impl(k, c, m, count, r, r_words, rng_seed, out, pipe);
     }
+    if (!crt && k->d_mul192 && !(flags & FTHE_ENC_FIXED_BASE))      // a 96-word n: r^n (1 + m n) on fthe_pow192
+        return encrypt_pow192(k, c, m, count, r, r_words, rng_seed, out, pipe);
     if (!crt && !k->pub_ok) return FTHE_ERR_UNSUPPORTED;
     if (flags & FTHE_ENC_FIXED_BASE) return encrypt_fb_impl(k, c, m, count, r, r_words, rng_seed, out, crt, pipe);
     // Device-drawn randomness under CRT draws y_p, y_q uniform in [1,p), [1,q) and
@@ -3360,6 +3365,10 @@ extern "C" int fthe_decrypt_short_dev(fthe_key *k, fthe_ctx *c, const uint32_t *
 // ---------------------------------------------------------------------------
 // Packed gradient pairs: one ciphertext per (g, h) (include/fthe.h)
 static dim3 grid256(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
+// a 96-word n whose encrypt would take the public path (fthe_pow192): the packed and slot calls stay unsupported there
+static bool pow192_only(const fthe_key *k, int flags) {
+    return k->d_mul192 && (!k->priv || (flags & FTHE_ENC_PUBLIC));
+}
 
 extern "C" int fthe_pack_gh_dev(fthe_ctx *c, const float *g, const float *h, size_t count, uint32_t *m) {
     if (!c || ((!g || !h || !m) && count)) return FTHE_ERR_ARG;
@@ -3385,6 +3394,7 @@ static int encrypt_gh_impl(fthe_key *k, fthe_ctx *c, const float *g, const float
                            int r_words, uint64_t rng_seed, uint64_t index0, uint32_t *out, int flags, HostPipe *pipe) {
     if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
     if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
+    if (pow192_only(k, flags)) return FTHE_ERR_UNSUPPORTED;
     HIPOK(hipSetDevice(c->device));
     int rc = c->gh[0].ensure(std::max<size_t>(4, count * FTHE_GH_PACKED_WORDS * 4));
     if (rc) return rc;
@@ -3453,6 +3463,7 @@ extern "C" int fthe_unpack_gh_slots_dev(fthe_ctx *c, const uint32_t *m, int stri
 static int encrypt_gh_slots_impl(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count, int slot_bits,
                                  int slots, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out, int flags,
                                  HostPipe *pipe) {
+    if (pow192_only(k, flags)) return FTHE_ERR_UNSUPPORTED;
     HIPOK(hipSetDevice(c->device));
     const size_t rows = (count + slots - 1) / slots;
     const int sw = slot_bits / 32, mww = slots * sw;
@@ -3703,28 +3714,113 @@ static int mul192_kway(fthe_key *k, fthe_ctx *c, const uint32_t *const *xs, int 
     if (!direct && count) HIPOK(hipMemcpyAsync(out, acc, bytes, hipMemcpyDeviceToDevice, c->stream));
     return mul192_end(c, (double)count * std::max(kk - 1, 1));
 }
-// x^e for one exponent, left to right in binary over whole-batch launches; x is kept in c->scratch, so out may be x
+// A call on fthe_pow192 (fthe_mul192.hip): out = x^e t for e >= 2 shared by the rows.  c->scratch
+// holds the odd-power tables of the slots, then the walk's byte string, then `extra` bytes of the caller's (the
+// drawn r of an encrypt).  The window: the largest table that fits the cap of fthe_ctx_set_mem_limit bounds w, and
+// among those widths the one with the fewest products runs.
+struct Pow192 {
+    fthe_ctx *c;
+    const fthe_key *k;
+    std::vector<uint8_t> sched;
+    int w = 0;
+    unsigned entries = 0;
+    uint64_t products = 0;
+    size_t table_bytes = 0, sched_bytes = 0;
+    uint32_t *table() const { return (uint32_t *)c->scratch.p; }
+    const uint32_t *dsched() const { return (const uint32_t *)((const char *)c->scratch.p + table_bytes); }
+    void *extra() const { return (char *)c->scratch.p + table_bytes + sched_bytes; }
+    // rows: the most rows one run() covers
+    int init(const mpz_t e, bool tail, size_t rows, size_t extra_bytes) {
+        int wmax = mul192::kPowMaxWindow;
+        sched_bytes = (2 * mpz_sizeinbase(e, 2) + 255) / 256 * 256;     // w = 1: a square and a product per bit
+        while (wmax > 1 && c->mem_limit &&
+               mul192::pow_table_bytes(rows, c->n_cu, wmax) + sched_bytes + extra_bytes > c->mem_limit)
+            wmax--;
+        w = mul192::pow_plan(e, tail, wmax, sched);
+        entries = mul192::pow_entries(sched);
+        products = mul192::pow_products(sched, tail);
+        table_bytes = mul192::pow_table_bytes(rows, c->n_cu, w);
+        // the stream is drained before the scratch may move and the walk is rewritten
+        HIPOK(hipStreamSynchronize(c->stream));
+        if (int rc = mul192_scratch(c, table_bytes + sched_bytes + extra_bytes)) return rc;
+        std::vector<uint8_t> padded(sched);
+        padded.resize((sched.size() + 3) / 4 * 4, 0);
+        HIPOK(hipMemcpy((char *)c->scratch.p + table_bytes, padded.data(), padded.size(), hipMemcpyHostToDevice));
+        return FTHE_OK;
+    }
+    int run(const uint32_t *x, int xw, const uint32_t *t, uint32_t *out, size_t cnt) const {
+        return mul192::launch_pow(c->stream, x, xw, t, out, k->d_mul192, dsched(), (uint32_t)sched.size(), entries,
+                                  products, table(), w, cnt, c->n_cu) == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+    }
+};
+// x^e for one exponent: e < 2 on fthe_mul192 (1 * 1, x * 1), else one walk on fthe_pow192.  A row is read and written
+// by one octet, so out may be exactly x and no copy of x is kept.
 static int mul192_pow(fthe_key *k, fthe_ctx *c, const uint32_t *x, const mpz_t e, size_t count, uint32_t *out) {
-    const size_t bytes = count * mul192::kWords * 4;
-    int rc = mul192_begin(c, k, mpz_sgn(e) ? bytes : 0);                             // e = 0 keeps no copy of x
+    int rc = mul192_begin(c, k);
     if (rc) return rc;
-    if (mpz_sgn(e) == 0) {
-        if ((rc = launch_mul192(c, k, nullptr, nullptr, out, count))) return rc;      // 1 * 1
+    if (mpz_cmp_ui(e, 2) < 0 || !count) {
+        if ((rc = launch_mul192(c, k, mpz_sgn(e) ? x : nullptr, nullptr, out, count))) return rc;
         return mul192_end(c, (double)count);
     }
-    uint32_t *base = (uint32_t *)c->scratch.p;
-    if (count) HIPOK(hipMemcpyAsync(base, x, bytes, hipMemcpyDeviceToDevice, c->stream));
-    if ((rc = launch_mul192(c, k, base, nullptr, out, count))) return rc;               // x mod n^2
-    double products = 1;
-    for (size_t i = mpz_sizeinbase(e, 2) - 1; i-- > 0;) {
-        if ((rc = launch_mul192(c, k, out, out, out, count))) return rc;
-        products += 1;
-        if (mpz_tstbit(e, i)) {
-            if ((rc = launch_mul192(c, k, out, base, out, count))) return rc;
-            products += 1;
+    Pow192 pw{c, k};
+    if ((rc = pw.init(e, false, count, 0)) || (rc = pw.run(x, mul192::kWords, nullptr, out, count))) return rc;
+    return mul192_end(c, (double)count * (double)pw.products);
+}
+
+// out[g] = 1 + m[g] n as a row of 2 nw words (g^m for g = n + 1), m a u64 or mw words; one thread per row, the
+// columns of the product summed in 96 bits.  m n + 1 <= (2^(32 nw) - 1)^2 + 1 fits the row.
+__global__ void k_one_plus_mn(const uint64_t *__restrict__ m64, const uint32_t *__restrict__ mw, int mww,
+                              const uint32_t *__restrict__ n, int nw, size_t count, uint32_t *__restrict__ out) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= count) return;
+    const int ml = m64 ? 2 : mww;
+    const uint64_t mv = m64 ? m64[g] : 0;
+    const uint32_t *mr = mw ? mw + g * (size_t)mww : nullptr;
+    uint32_t *o = out + g * 2 * (size_t)nw;
+    uint64_t lo = 1;
+    uint32_t hi = 0;
+    for (int j = 0; j < 2 * nw; j++) {
+        for (int i = j < nw ? 0 : j - nw + 1; i < ml && i <= j; i++) {
+            const uint32_t mi = m64 ? (uint32_t)(mv >> (32 * i)) : mr[i];
+            const uint64_t p = (uint64_t)mi * n[j - i];
+            lo += p;
+            hi += lo < p;
         }
+        o[j] = (uint32_t)lo;
+        lo = lo >> 32 | (uint64_t)hi << 32;
+        hi = 0;
     }
-    return mul192_end(c, (double)count * products);
+}
+
+// The public-key encrypt of a 96-word n (public keys, and key holders under FTHE_ENC_PUBLIC):
+// c = (1 + m n) r^n mod n^2, chunk by chunk: r drawn into the scratch (or injected), 1 + m n into out, then one
+// fthe_pow192 call with x = r, e = n, t = out, in place.  The draw is encrypt_impl's: same key, same m.idx0 + off.
+static int encrypt_pow192(fthe_key *k, fthe_ctx *c, const MsgSrc &m, size_t count, const uint32_t *r, int r_words,
+                          uint64_t rng_seed, uint32_t *out, HostPipe *pipe) {
+    int rc = mul192_begin(c, k);
+    if (rc || !count) return rc ? rc : mul192_end(c, 0);
+    const int nw = k->n_words;
+    const size_t L = mul192_chunk_rows(), cw = mul192::kWords;
+    Pow192 pw{c, k};
+    if ((rc = pw.init(k->n, true, std::min(L, count), r ? 0 : std::min(L, count) * nw * 4))) return rc;
+    RngKey rk{};
+    if (!r) rk = make_rng_key(rng_seed, 0);
+    for (size_t off = 0; off < count; off += L) {
+        const size_t cnt = std::min(L, count - off);
+        if (pipe && (rc = pipe->before(off, L, count))) return rc;
+        const uint32_t *rw = r + (r ? off * r_words : 0);
+        int rwn = r_words;
+        if (!r) {
+            hipLaunchKernelGGL(k_rng_r, grid256(cnt), dim3(256), 0, c->stream, k->d_nwords, nw, k->n_bits, rk,
+                               m.idx0 + off, cnt, (uint32_t *)pw.extra());
+            rw = (const uint32_t *)pw.extra(); rwn = nw;
+        }
+        hipLaunchKernelGGL(k_one_plus_mn, grid256(cnt), dim3(256), 0, c->stream, m.m64 ? m.m64 + off : nullptr,
+                           m.mw ? m.mw + off * (size_t)m.mww : nullptr, m.mww, k->d_nwords, nw, cnt, out + off * cw);
+        if ((rc = pw.run(rw, rwn, out + off * cw, out + off * cw, cnt))) return rc;
+        if (pipe && (rc = pipe->after(off, cnt))) return rc;
+    }
+    return mul192_end(c, (double)count * (double)pw.products);
 }
 
 // Test hook (include/fthe.h): the per-key context bytes of fthe_mul192, host only.
@@ -5396,6 +5492,7 @@ extern "C" int fthe_decrypt_shared(fthe_key *k, const uint32_t *ct, size_t count
 extern "C" int fthe_encrypt_shared(fthe_key *k, const uint64_t *m, size_t count, uint32_t *out, int flags) {
     if (!k || ((!m || !out) && count)) return FTHE_ERR_ARG;
     if (!count) return FTHE_OK;
+    if (pow192_only(k, flags) && !(flags & (FTHE_ENC_FIXED_BASE | FTHE_ENC_FIXED_BASE_EXACT))) return FTHE_ERR_UNSUPPORTED;
     Coalescer *co = key_coalescer(k);
     if (!co) return FTHE_ERR_NOMEM;
     EncReq r{m, count, out, flags};

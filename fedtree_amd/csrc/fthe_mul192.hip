@@ -19,7 +19,8 @@
 //      conditional subtraction of N mod 2^6144 with the borrow resolved across the octet, rows stored.  Every operand row of a batch is loaded before any is stored.
 //
 // fthe_gprod192, below it, is the gathered 8-way product on the same routines: steps 2 and 3 per member with the
-// remainder kept in LDS as the next multiplier, steps 1 and 4 once per group.
+// remainder kept in LDS as the next multiplier, steps 1 and 4 once per group.  fthe_pow192, the third
+// kernel, walks a whole exponent that way: x^e t by sliding windows over a table of odd powers.
 #include <algorithm>
 #include <utility>
 
@@ -331,7 +332,187 @@ __global__ __launch_bounds__(64 * kWaves) void fthe_gprod192_kernel(const uint32
     }
 }
 
+// fthe_pow192: out[g] = x[g]^e t[g] mod N for one exponent e >= 2 shared by the batch (t null: 1), the power behind
+// the public-key encrypt r^n (1 + m n) and the uniform scalar mul.  The geometry above; an octet owns
+// one row for the whole walk, with the running value resident in LDS as the multiplier column, as in fthe_gprod192:
+//
+//   base: a row of xw <= 192 words, zero-extended -> staging words -> limbs x in registers; one product by the
+//   column 1 and step 3 leave x as a lazy remainder in [0, 2N) in area[0, 228).
+//   table: odd powers x^1, x^3, ..., entry j = x^(2 j - 1), as lazy limb rows in global memory, the lane's 29 limbs
+//   padded to 32 words (eight 16-byte pieces), one table per slot (workgroup, wave, octet).  A lane reads back only
+//   what it wrote itself.  x^2 is formed once and parked in the last entry's place; entry k + 1 = x^2 * entry k with
+//   entry k still lying in area as the multiplier column (k = 1: the column is x^2, the registers hold entry 1), the
+//   last product overwriting x^2's place.
+//   walk: the host's byte string (pow_schedule), read with scalar loads: byte 0 names the entry that becomes the
+//   column; then 0 = square, the registers taking the column itself (xl[i] = area[29 l + i]: nothing is re-limbed),
+//   j = multiply, the registers taking entry j from global memory; each is product<kFull>(xl, area, area) and step 3.
+//   Nothing is converted, subtracted or stored between products.  Both factors are lazy now: z < 2^12290, for which
+//   the cut points hold (tools/mul192_model.py power()).
+//   tail: t's row through the staging words as a gathered member, one more product; then step 4 and the store.
+//
+// A row is read and written by its octet alone, the base before anything else and t after the walk: out may be
+// exactly t, or exactly x when xw = 192.  An idle octet of the last batch repeats the last row and stores nothing.
+__device__ inline void load_base(const uint32_t *x, int xw, bool vec, uint64_t row, int l, uint4 (&v)[6]) {
+    const uint32_t *p = x + row * (uint64_t)xw;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        const int w0 = 4 * (8 * k + l);
+        if (vec) {
+            v[k] = w0 < xw ? *(const uint4 *)(p + w0) : make_uint4(0, 0, 0, 0);
+        } else {
+            v[k].x = w0 < xw ? p[w0] : 0;
+            v[k].y = w0 + 1 < xw ? p[w0 + 1] : 0;
+            v[k].z = w0 + 2 < xw ? p[w0 + 2] : 0;
+            v[k].w = w0 + 3 < xw ? p[w0 + 3] : 0;
+        }
+    }
+}
+
+// the lane's limbs of the multiplier column (a lazy remainder) -> registers
+__device__ inline void column_of(const uint32_t *area, int l, uint32_t (&xl)[kPerLane]) {
+    const uint32_t *a = area + kPerLane * opaque(l);
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) xl[i] = a[i];
+}
+
+// the lane's 128 bytes of table entry j (from 0) of its octet's table
+__device__ inline uint4 *entry_at(uint32_t *table, uint32_t slot0, uint32_t stride, uint32_t j, int lane) {
+    const int ln = opaque(lane);
+    return (uint4 *)(table + ((uint64_t)(slot0 + (ln >> 3)) * stride + j) * kEntryWords + 32 * (ln & 7));
+}
+__device__ inline void entry_store(uint4 *e, const uint32_t *area, int l) {
+    const uint32_t *a = area + kPerLane * opaque(l);
+#pragma unroll
+    for (int k = 0; k < 7; k++) e[k] = make_uint4(a[4 * k], a[4 * k + 1], a[4 * k + 2], a[4 * k + 3]);
+    e[7] = make_uint4(a[28], 0, 0, 0);
+}
+__device__ inline void entry_load(const uint4 *e, uint32_t (&xl)[kPerLane]) {
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        const uint4 q = e[k];
+        xl[4 * k] = q.x; xl[4 * k + 1] = q.y; xl[4 * k + 2] = q.z; xl[4 * k + 3] = q.w;
+    }
+    xl[28] = e[7].x;
+}
+
+__global__ __launch_bounds__(64 * kWaves) void fthe_pow192_kernel(const uint32_t *x, int xw, int vec, const uint32_t *t,
+                                                                  uint32_t *out, const uint32_t *kctx,
+                                                                  const uint32_t *__restrict__ sched, uint32_t slen,
+                                                                  uint32_t *table, uint32_t stride, uint32_t entries,
+                                                                  uint64_t count, uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint32_t slot0 = __builtin_amdgcn_readfirstlane((blockIdx.x * kWaves + wave) * kRowsPerWave);
+    const uint64_t nbatch = (count + kRowsPerWave - 1) / kRowsPerWave;
+    for (;;) {
+        uint32_t tk = 0;
+        if (lane == 0) tk = atomicAdd(&s_next, 1u);
+        tk = __builtin_amdgcn_readfirstlane(tk);
+        const uint64_t batch = blockIdx.x + (uint64_t)tk * nwg;
+        if (batch >= nbatch) break;
+        // the octet's row, recomputed where it is used rather than kept across the products
+        auto row_of = [&](bool &live) {
+            uint64_t row = batch * kRowsPerWave + (uint32_t)(opaque(lane) >> 3);
+            live = row < count;
+            return live ? row : count - 1;
+        };
+        uint32_t xl[kPerLane];
+        {
+            bool live;
+            uint4 v[6];
+            load_base(x, xw, vec != 0, row_of(live), l, v);
+            stage(area, v, l);
+        }
+        wave_sync();
+        // One product site for the whole walk; every condition below is uniform.  Steps [0, nbuild): the base by 1
+        // (-> entry 1), then x^2 (parked in the last entry's place) and x^2 times the entry before (-> entries 2 ..);
+        // steps [nbuild, nbuild + slen - 1): the schedule's bytes 1 ..; a last step for t.
+        const uint32_t nbuild = entries > 1 ? entries + 1 : 1, nwalk = nbuild + slen - 1, total = nwalk + (t ? 1 : 0);
+#pragma unroll 1
+        for (uint32_t s = 0; s < total; s++) {
+            if (s == 0 || s >= nwalk) {
+                if (s) {
+                    bool live;
+                    uint4 v[6];
+                    load_row(t, row_of(live), l, v);
+                    stage(area, v, l);             // over the spent high limbs of the step before
+                    wave_sync();
+                }
+                limbs_of(area, l, xl);
+                wave_sync();
+                if (s == 0) {
+#pragma unroll
+                    for (int i = 0; i < kPerLane; i++) area[kPerLane * l + i] = (lane0 && i == 0) ? 1u : 0u;
+                }
+            } else {
+                uint32_t j = 0;                    // 0: square, else times entry j
+                if (s >= nbuild) {
+                    const uint32_t i = s - nbuild + 1;
+                    j = (sched[i >> 2] >> (8 * (i & 3))) & 0xffu;
+                } else if (s > 1) {
+                    j = s == 2 ? 1 : entries;
+                }
+                j = __builtin_amdgcn_readfirstlane(j);
+                if (j == 0) column_of(area, l, xl);
+                else entry_load(entry_at(table, slot0, stride, j - 1, lane), xl);
+            }
+            wave_sync();
+            product<kFull>(xl, area, area, lane0, top);
+            barrett(xl, area, s_mu, s_nl, l, lane0, top);
+            if (s < nbuild) {
+                entry_store(entry_at(table, slot0, stride, s == 0 ? 0 : s == 1 ? entries - 1 : s - 1, lane), area, l);
+                if (s + 1 == nbuild) {             // the table is whole: the schedule's first byte names the seed
+                    entry_load(entry_at(table, slot0, stride, (sched[0] & 0xffu) - 1, lane), xl);
+                    wave_sync();
+#pragma unroll
+                    for (int i = 0; i < kPerLane; i++) area[kPerLane * l + i] = xl[i];
+                    wave_sync();
+                }
+            }
+        }
+        uint32_t r[24];
+        canonical_dwords(area, s_nd, l, lane0, r);
+        bool live;
+        const uint64_t row = row_of(live);
+        if (live) {
+            uint4 *p = (uint4 *)(out + row * kWords + 24 * l);
+#pragma unroll
+            for (int k = 0; k < 6; k++) p[k] = make_uint4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+        }
+        wave_sync();
+    }
+}
+
 }  // namespace
+
+int launch_pow(hipStream_t st, const uint32_t *x, int xw, const uint32_t *t, uint32_t *out, const void *kctx,
+               const uint32_t *sched, uint32_t slen, unsigned entries, uint64_t products, uint32_t *table, int w,
+               size_t count, int n_cu) {
+    if (count == 0) return hipSuccess;
+    if (xw <= 0 || xw > kWords || w < 1 || w > kPowMaxWindow || !slen || entries < 1 || entries > (1u << (w - 1)))
+        return hipErrorInvalidValue;
+    const int vec = xw % 4 == 0 && (uintptr_t)x % 16 == 0;
+    const unsigned blocks = pow_blocks(count, n_cu);
+    const size_t per = std::min<size_t>((size_t)blocks * kPerWg * (size_t)std::max<uint64_t>(1, kPowBudget / products),
+                                        (size_t)1 << 22);
+    for (size_t off = 0; off < count; off += per) {
+        const size_t cnt = std::min(per, count - off);
+        hipLaunchKernelGGL(fthe_pow192_kernel, dim3(pow_blocks(cnt, n_cu)), dim3(64 * kWaves), 0, st,
+                           x + off * (size_t)xw, xw, vec, t ? t + off * kWords : nullptr, out + off * kWords,
+                           (const uint32_t *)kctx, sched, slen, table, 1u << (w - 1), entries, (uint64_t)cnt,
+                           pow_blocks(cnt, n_cu));
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
 
 int launch_gather(hipStream_t st, const uint32_t *src, const int64_t *gidx, uint32_t *dst, const void *kctx, size_t count,
                   int n_cu) {

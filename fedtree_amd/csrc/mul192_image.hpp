@@ -61,4 +61,67 @@ int launch(hipStream_t st, const uint32_t *x, const uint32_t *y, uint32_t *out, 
 int launch_gather(hipStream_t st, const uint32_t *src, const int64_t *gidx, uint32_t *dst, const void *kctx, size_t count,
                   int n_cu);
 
+// ---- fthe_pow192: out[g] = x[g]^e t[g] mod N for one exponent e >= 2 shared by the batch ----
+// The walk is sliding-window exponentiation over a table of odd powers, entry j = x^(2 j - 1), j = 1 ..; the host
+// writes it as one byte string: byte 0 is the entry that seeds the running value, every further byte is 0 for a square
+// or j for a product by entry j.  Restates tools/mul192_model.py schedule() / products() / plan() exactly.
+constexpr int kPowMaxWindow = 5;
+constexpr int kEntryWords = 32 * kLanes;       // a table entry: each lane's 29 limbs padded to 32 words (1,024 B)
+constexpr uint64_t kPowBudget = 16384;         // products a wave runs in one launch, at most (one batch runs whole)
+
+inline std::vector<uint8_t> pow_schedule(const mpz_t e, int w) {
+    std::vector<uint8_t> s;
+    for (long i = (long)mpz_sizeinbase(e, 2) - 1; i >= 0;) {
+        if (!mpz_tstbit(e, (mp_bitcnt_t)i)) { s.push_back(0); i--; continue; }
+        long lo = i - w + 1 > 0 ? i - w + 1 : 0;
+        while (!mpz_tstbit(e, (mp_bitcnt_t)lo)) lo++;
+        unsigned v = 0;
+        for (long b = i; b >= lo; b--) v = 2 * v + (unsigned)mpz_tstbit(e, (mp_bitcnt_t)b);
+        if (!s.empty()) s.insert(s.end(), (size_t)(i - lo + 1), 0);
+        s.push_back((uint8_t)((v + 1) / 2));
+        i = lo - 1;
+    }
+    return s;
+}
+// entries built: the highest one the walk uses
+inline unsigned pow_entries(const std::vector<uint8_t> &s) {
+    unsigned m = 1;
+    for (uint8_t b : s) m = b > m ? b : m;
+    return m;
+}
+// products per row: the base by 1, the table (x^2, then one per further entry), the walk, the tail
+inline uint64_t pow_products(const std::vector<uint8_t> &s, bool tail) {
+    const unsigned E = pow_entries(s);
+    return 1 + (E > 1 ? E : 0) + (s.size() - 1) + (tail ? 1 : 0);
+}
+// the width in 1 .. wmax with the fewest products, the smaller one on a tie
+inline int pow_plan(const mpz_t e, bool tail, int wmax, std::vector<uint8_t> &sched) {
+    int best = 0;
+    uint64_t cost = 0;
+    for (int w = 1; w <= wmax; w++) {
+        std::vector<uint8_t> s = pow_schedule(e, w);
+        const uint64_t c = pow_products(s, tail);
+        if (!best || c < cost) { best = w; cost = c; sched.swap(s); }
+    }
+    return best;
+}
+// workgroups of a launch over count rows, and the table's bytes for w: a table per slot (workgroup, wave, octet)
+inline unsigned pow_blocks(size_t count, int n_cu) {
+    const size_t cu = (size_t)(n_cu > 1 ? n_cu : 1), wg = (count + kPerWg - 1) / kPerWg;
+    return (unsigned)(wg < cu ? wg : cu);
+}
+inline size_t pow_table_bytes(size_t count, int n_cu, int w) {
+    return (size_t)pow_blocks(count, n_cu) * kPerWg * ((size_t)1 << (w - 1)) * kEntryWords * 4;
+}
+
+// One call: count rows in launches of at most blocks * 64 * max(1, kPowBudget / products) rows (2^22 at most).
+// x: rows of xw <= 192 words, zero-extended (read in 16-byte pieces when xw % 4 == 0 and x is 16-byte aligned); t:
+// rows of 192 words or null (the integer 1); out: rows of 192 words, canonical; out may be exactly t, or exactly x
+// when xw == 192.  sched: the device copy of pow_schedule()'s slen bytes, padded to whole words; table: device bytes
+// of pow_table_bytes(count, n_cu, w), 16-byte aligned; entries, products: pow_entries() and pow_products() of the
+// schedule.  Returns a hipError_t.
+int launch_pow(hipStream_t st, const uint32_t *x, int xw, const uint32_t *t, uint32_t *out, const void *kctx,
+               const uint32_t *sched, uint32_t slen, unsigned entries, uint64_t products, uint32_t *table, int w,
+               size_t count, int n_cu);
+
 }  // namespace mul192

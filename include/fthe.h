@@ -100,9 +100,18 @@ void  fthe_host_free(void *p);
  * on any rows of 192 words (rows >= n^2 included), results in [0, n^2); out may alias as for the other sizes, and
  * the _dev forms want their row arrays 16-byte aligned (the kernel moves rows in 16-byte pieces; any hipMalloc'd
  * or torch buffer, and any whole-row offset into one, is).  fthe_reduce_kway_dev with an out that overlaps a plane
- * other than exactly plane 0 or 1, and the scalar muls with e > 0, keep count x 768 B in the context's scratch,
- * under fthe_ctx_set_mem_limit (FTHE_ERR_NOMEM above it).  The host add is staged in chunks of 65,536 rows
- * (FTHE_MUL192_CHUNK overrides, read per call).  The gathered 8-way product of such rows runs on a second kernel of
+ * other than exactly plane 0 or 1 keeps count x 768 B in the context's scratch, under fthe_ctx_set_mem_limit
+ * (FTHE_ERR_NOMEM above it).  The scalar muls with e >= 2 run on a third kernel of that file (fthe_pow192: one
+ * launch walks the whole exponent by sliding windows, the running value resident in LDS); they keep no copy of x
+ * (out may be exactly x), and their scratch is the odd-power tables of the launch's slots,
+ * min(ceil(count / 64), CUs) x 64 x 2^(w-1) x 1024 B for a window of w <= 5 bits (268 MB at w = 5 on 256 CUs),
+ * plus the walk's bytes: under the limit the widest window that fits is taken, FTHE_ERR_NOMEM if w = 1 does not.
+ * On the same kernel runs the public-key encrypt, c = (1 + m n) r^n mod n^2:
+ *     fthe_encrypt_u64[_at][_dev], fthe_encrypt_words[_dev]
+ * on a public key, or a key holder's with FTHE_ENC_PUBLIC, without the fixed-base flags; r injected (r_words of
+ * 1..96, zero-extended) or drawn on the device exactly as at the other sizes (same stream, same index0), in chunks
+ * of 65,536 rows whose r (chunk x 384 B) lies in the scratch behind the tables.  The host add and the host encrypts
+ * are staged in chunks of 65,536 rows (FTHE_MUL192_CHUNK overrides, read per call).  The gathered 8-way product of such rows runs on a second kernel of
  * that file (fthe_gprod192: the running product stays in LDS between a group's members), and with it
  *     fthe_reduce_segments[_dev], fthe_reduce_segments_csr_dev, fthe_reduce_segments_zero_first_dev,
  *     fthe_histogram_dev, fthe_histogram_zero_first_dev, fthe_scan_segments[_dev]
@@ -111,7 +120,8 @@ void  fthe_host_free(void *p);
  * Every other call that works mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits,
  * fthe_invert, fthe_sub_inv, fthe_scalar_mul_rows, fthe_dot_segments, the
  * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the packed and slot-packed pair
- * calls, the public-key encrypt, and fthe_add_shared / fthe_scalar_mul_u64_shared.  A key holder's CRT encrypt
+ * calls, the public-key encrypt with a fixed-base flag, and fthe_add_shared / fthe_scalar_mul_u64_shared /
+ * fthe_encrypt_shared on the public path.  A key holder's CRT encrypt
  * and decrypt at this size run mod p^2, q^2 as before; they are not part of this paragraph's claim.
  * n of 2049..3040 bits stays FTHE_ERR_UNSUPPORTED.
  */

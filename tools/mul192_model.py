@@ -21,6 +21,9 @@ kernel forms r modulo 2^(27 * 228) (2N < 2^6145), limb by limb in the borrow cha
 2^6144, one bit more than a row: the subtraction runs on the row's 192 dwords, and is taken when it leaves no
 borrow or when that bit (limb 227, bit 15) is set.
 
+chain() is the gathered product of fthe_gprod192 (one lazy factor per product), power() the sliding-window walk of
+fthe_pow192 (both factors lazy) with its schedule builder: schedule(), products(), plan().
+
 Run:  python tools/mul192_model.py [seed] [trials]
 """
 import random
@@ -179,6 +182,111 @@ def chain(rows, n, lanes=False):
     return row
 
 
+MAX_WINDOW = 5
+
+
+def schedule(e, w):
+    """the walk of fthe_pow192 for e >= 1 as one byte string (mul192_image.hpp pow_schedule restates it): sliding
+    windows of at most w bits over a table of odd powers, entry j = x^(2 j - 1).  Byte 0 is the entry that seeds the
+    running value; every further byte is 0 for a square or j for a product by entry j."""
+    assert e >= 1 and 1 <= w <= MAX_WINDOW
+    s, i = [], e.bit_length() - 1
+    while i >= 0:
+        if not (e >> i) & 1:
+            s.append(0)
+            i -= 1
+            continue
+        lo = max(i - w + 1, 0)
+        while not (e >> lo) & 1:
+            lo += 1
+        v = (e >> lo) & ((1 << (i - lo + 1)) - 1)
+        if s:
+            s += [0] * (i - lo + 1)
+        s.append((v + 1) // 2)
+        i = lo - 1
+    return bytes(s)
+
+
+def products(sched, tail):
+    """products per row: the base by 1, the table (x^2, then one per entry after the first; only the entries the
+    walk uses are built), the walk, and the tail's product by t"""
+    entries = max(sched)
+    return 1 + (entries if entries > 1 else 0) + len(sched) - 1 + (1 if tail else 0)
+
+
+def plan(e, tail=False, wmax=MAX_WINDOW):
+    """(w, schedule) with the fewest products among w = 1 .. wmax, the smaller w on a tie"""
+    return min(((w, schedule(e, w)) for w in range(1, wmax + 1)), key=lambda p: (products(p[1], tail), p[0]))
+
+
+def power(x, e, n, t=None, w=None, lanes=False, count=None):
+    """x^e t mod n^2 as fthe_pow192 forms it, e >= 2, x any row of at most 192 words, t any row or None
+    (the integer 1); w: the window width, None for plan()'s.  Every product multiplies registers xl by the multiplier
+    column r, and from the second product on both are lazy remainders below 2N <= 2^6145:
+        z  = xl r             < 2^12290 < 2^(a + b) = 2^12312
+        z1 = floor(z / 2^a)   < 2^6215 < 2^(27 * 231)
+        q  = floor(z1 mu/2^b) <= z / N < 2^6210 = 2^(27 * 230)
+        z1 mu                 < 2^(6215 + 6232) < 2^(27 * 464)
+        z1 mu / 2^b > z / N - z / 2^(a+b) - 2^a / N > z / N - 2^-22 - 2^-5
+    so q is floor(z / N) or one below it and r = z - q N stays in [0, 2N) with limbs 228..231 zero.  Each bound, and
+    ring()'s column sum below 2^62 where lanes is set, is asserted at every product.  count: a list that receives the
+    number of products run.  Returns the canonical result."""
+    assert n_ok(n) and e >= 2 and 0 <= x < 1 << (32 * WORDS) and (t is None or 0 <= t < 1 << (32 * WORDS))
+    N = n * n
+    mu = mu_of(N)
+    prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
+    ran = [0]
+
+    def step(xl, r):
+        """registers xl times the multiplier column r -> the lazy remainder"""
+        assert xl < 1 << 6145 and r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
+        z = prod(xl, r)
+        assert z == xl * r and z < 1 << 12290
+        z1 = z >> (B * SHIFT_A)
+        assert z1 < 1 << (B * SHIFT_B)
+        zm = prod(z1, mu)
+        assert zm < 1 << (B * 2 * LIMBS)
+        q = zm >> (B * SHIFT_B)
+        assert q < 1 << (B * 230) and z // N - 1 <= q <= z // N
+        if lanes:
+            low = ring(limbs(q), limbs(N), drain=False)
+            zl, rl, borrow = limbs(z, 2 * LIMBS), [], 0
+            for s in range(LIMBS):
+                d = (zl[s] - low[s] - borrow) & 0xFFFFFFFF
+                borrow = d >> 31
+                rl.append(d & MASK if s < R_LIMBS else 0)
+            out = value(rl)
+        else:
+            out = (z - q * N) % (1 << (B * R_LIMBS))
+        assert out == z - q * N and 0 <= out < 2 * N
+        ran[0] += 1
+        return out
+
+    sched = schedule(e, w) if w else plan(e, t is not None)[1]
+    entries = max(sched)
+    table = [step(x, 1)]                                  # the base by 1: entry 1
+    if entries > 1:
+        r = step(table[0], table[0])                      # x^2, parked in the last entry's place
+        x2 = r
+        for k in range(1, entries):
+            r = step(table[0] if k == 1 else x2, r)       # x^2 times the entry before (k = 1: x times x^2)
+            table.append(r)
+    r = table[sched[0] - 1]
+    for j in sched[1:]:
+        r = step(table[j - 1] if j else r, r)
+    if t is not None:
+        r = step(t, r)
+    assert ran[0] == products(sched, t is not None)
+    if count is not None:
+        count.append(ran[0])
+    row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
+    assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
+    if high or row >= N:
+        row = (row - N) % (1 << (32 * WORDS))
+    assert row == pow(x, e, N) * (1 if t is None else t) % N
+    return row
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -190,6 +298,8 @@ def main():
             x, y = rng.getrandbits(32 * WORDS), rng.getrandbits(32 * WORDS)
             mul(x, y, n, lanes=trials <= 4)
         chain([top] * 3 + [rng.getrandbits(32 * WORDS) for _ in range(5)], n, lanes=trials <= 4)
+        power(top, n, n, t=top)
+        power(rng.getrandbits(32 * WORDS), rng.getrandbits(12) | 2, n, w=3, lanes=trials <= 4)
     print("mul192 model: ok")
 
 
