@@ -4218,6 +4218,10 @@ struct InvTree {
     // out = x y mod n^2 over cnt contiguous rows; out may be exactly x or y.
     int mul(const uint32_t *x, const uint32_t *y, uint32_t *out, size_t cnt) {
         if (!cnt) return FTHE_OK;
+        if (k->d_mul192) {                  // Paillier-3072: the product on fthe_mul192
+            Lc.mm += (double)cnt;
+            return launch_mul192(c, k, x, y, out, cnt);
+        }
         if (k->d_addb && c->fn_addb) {
             Lc.mm += (double)cnt;
             return launch_addb(c, k, x, y, out, cnt);
@@ -4323,15 +4327,119 @@ struct InvTree {
         return mul(hi, a + h * cw, out + h * cw, f);
     }
 };
+
+// Paillier-3072: the same inverse as a radix-8 tree on fthe_inv192_up / fthe_inv192_down (fthe_mul192.hip; DESIGN.md
+// 25).  One tree per chunk.  Level l + 1 has a row per group of 8 rows of level l; the first level of at most 8 rows
+// goes to the host (InvTree::invert_top) and comes back inverted; going down, a level's inverses overwrite its rows.
+// Workspace (c->scratch, mul192::inv_ws_bytes): the rows of the levels above level 0, lowest first; every level's
+// prefix entries, lowest first; the slots' parking entries.
+struct Inv192 {
+    fthe_key *k; fthe_ctx *c;
+    std::vector<size_t> ms;                 // rows of level 0 .. t
+    std::vector<uint32_t *> rows, pre;      // rows[l]: level l (rows[0]: the chunk's x, or the top's buffer when t = 0)
+    uint32_t *park = nullptr;
+    double mm = 0;
+
+    void shape(const uint32_t *x, size_t m) {
+        ms = mul192::inv_levels(m);
+        const size_t t = ms.size() - 1;
+        rows.assign(t + 1, nullptr); pre.assign(t + 1, nullptr);
+        uint32_t *at = (uint32_t *)c->scratch.p;
+        rows[0] = t ? const_cast<uint32_t *>(x) : at;
+        if (!t) at += m * mul192::kWords;
+        for (size_t l = 1; l <= t; l++) { rows[l] = at; at += ms[l] * mul192::kWords; }
+        for (size_t l = 0; l < t; l++) { pre[l] = at; at += ms[l + 1] * (mul192::kInvRadix - 1) * mul192::kEntryWords; }
+        park = at;
+    }
+    // Up-sweep of the chunk x (m rows); fetch: the top level's rows arrive in `top` (pinned), the stream drained.
+    int up(const uint32_t *x, size_t m, uint32_t *top, bool fetch) {
+        shape(x, m);
+        const size_t t = ms.size() - 1;
+        for (size_t l = 0; l < t; l++) {
+            if (mul192::launch_inv_up(c->stream, rows[l], pre[l], rows[l + 1], k->d_mul192, ms[l], c->n_cu) != hipSuccess)
+                return FTHE_ERR_HIP;
+            mm += 7.0 * (double)ms[l + 1];
+        }
+        if (!fetch) return FTHE_OK;
+        HIPOK(hipMemcpyAsync(top, t ? rows[t] : x, ms[t] * mul192::kWords * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));
+        return FTHE_OK;
+    }
+    // Down-sweep from the inverted top (pinned host rows); a == nullptr: out = x^-1, else out = a x^-1.
+    int down(const uint32_t *top, const uint32_t *a, uint32_t *out) {
+        const size_t t = ms.size() - 1;
+        HIPOK(hipMemcpyAsync(!t && !a ? out : rows[t], top, ms[t] * mul192::kWords * 4, hipMemcpyHostToDevice, c->stream));
+        if (!t) {
+            if (a) mm += (double)ms[0];
+            return a ? launch_mul192(c, k, rows[0], a, out, ms[0]) : FTHE_OK;
+        }
+        for (size_t l = t; l-- > 0;) {
+            const bool last = l == 0;
+            if (mul192::launch_inv_down(c->stream, rows[l], last ? a : nullptr, rows[l + 1], pre[l], park,
+                                        last ? out : rows[l], k->d_mul192, ms[l], c->n_cu) != hipSuccess)
+                return FTHE_ERR_HIP;
+            mm += (last && a ? 22.0 : 14.0) * (double)ms[l + 1];
+        }
+        return FTHE_OK;
+    }
+};
 }  // namespace
+
+static int invert192(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *x, size_t count, mpz_srcptr cfac,
+                     uint32_t *out) {
+    auto ws = [&](size_t m) { return mul192::inv_ws_bytes(m, mul192::inv_blocks(m, c->n_cu)); };
+    size_t chunk = std::min(inv_chunk_rows(), std::max<size_t>(count, 1));
+    if (c->mem_limit && ws(chunk) > c->mem_limit && ws(chunk) > c->scratch.n) {
+        // the workspace grows with the rows: the most rows whose tree fits the limit
+        const size_t lim = std::max(c->mem_limit, c->scratch.n);
+        if (ws(1) > lim) return FTHE_ERR_NOMEM;
+        size_t lo = 1, hi = chunk;              // ws(lo) fits, ws(hi) does not
+        while (hi - lo > 1) {
+            const size_t mid = lo + (hi - lo) / 2;
+            (ws(mid) <= lim ? lo : hi) = mid;
+        }
+        chunk = lo;
+    }
+    int rc = mul192_begin(c, k, count ? ws(chunk) : 0);
+    if (rc || !count) return rc ? rc : mul192_end(c, 0);
+    const size_t cw = mul192::kWords, nch = (count + chunk - 1) / chunk, top_words = mul192::kInvRadix * cw;
+    if ((rc = c->inv_top.ensure(nch * top_words * 4))) return rc;
+    Inv192 T{k, c};
+    InvTree host{k, c};                         // the top's inversion on the host is the tree's own
+    host.cw = cw;
+    uint32_t *tops = (uint32_t *)c->inv_top.p;
+    for (size_t j = 0; j < nch; j++) {
+        const size_t off = j * chunk, m = std::min(chunk, count - off);
+        if ((rc = T.up(x + off * cw, m, tops + j * top_words, true))) return rc;
+        host.ms.assign(1, T.ms.back());
+        if ((rc = host.invert_top(tops + j * top_words, cfac))) return rc;
+        if (nch == 1 && (rc = T.down(tops, a, out))) return rc;
+    }
+    for (size_t j = 0; nch > 1 && j < nch; j++) {
+        const size_t off = j * chunk, m = std::min(chunk, count - off);
+        if ((rc = T.up(x + off * cw, m, nullptr, false))) return rc;
+        if ((rc = T.down(tops + j * top_words, a ? a + off * cw : nullptr, out + off * cw))) return rc;
+    }
+    return mul192_end(c, T.mm);
+}
 
 // a == nullptr: the inverse alone.  Several chunks: every chunk's up-sweep and host inversion runs before any chunk's
 // down-sweep (a non-unit fails the call with out untouched), so each chunk's up-sweep runs twice.
+// A 96-word n runs this binary tree on fthe_mul192, which measured faster at every size tried;
+// FTHE_INV192_TREE=0 (read per call) sends it to invert192, the radix-8 kernels, byte-identical.
 static int invert_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *x, size_t count,
                        const uint32_t *offset, int offset_words, uint32_t *out) {
     if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
     if (offset_words < 0 || offset_words > k->n_words) return FTHE_ERR_ARG;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
+    Mpz cfac;
+    const bool shifted = offset && offset_words > 0;
+    if (shifted) {
+        mpz_from_words(cfac, offset, offset_words);
+        mpz_mul(cfac, cfac, k->n); mpz_add_ui(cfac, cfac, 1); mpz_mod(cfac, cfac, k->n2);
+    }
+    const char *arm = k->d_mul192 ? getenv("FTHE_INV192_TREE") : nullptr;
+    if (arm && arm[0] == '0') return invert192(k, c, a, x, count, shifted ? (mpz_srcptr)cfac : nullptr, out);
     InvTree T{k, c};
     T.cw = 2 * (size_t)k->n_words;
     const size_t row = T.cw * 4;
@@ -4344,8 +4452,9 @@ static int invert_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32
     }
     // (the matrix-core add reads and writes rows only: no slot region to speak of)
     const bool addb = k->d_addb && c->fn_addb;
-    int rc = k->rowio ? begin_call(c, k, addb ? 1 : chunk, T.Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
-                      : begin_call(c, k, chunk, T.Lc, nslots_for(k), k->sn2);
+    int rc = k->d_mul192 ? mul192_begin(c, k)
+             : k->rowio  ? begin_call(c, k, addb ? 1 : chunk, T.Lc, SL_C0 + 1, k->sn2, rowio_chunk_lanes())
+                         : begin_call(c, k, chunk, T.Lc, nslots_for(k), k->sn2);
     if (rc) return rc;
     if (count == 0) return end_call(c, T.Lc);
     const size_t nch = (count + chunk - 1) / chunk, top_words = kInvTop * T.cw;
@@ -4353,13 +4462,7 @@ static int invert_impl(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32
     T.A = (uint32_t *)c->scratch.p;
     T.B[0] = T.A + (chunk + 64) * T.cw;
     T.B[1] = T.B[0] + ((chunk + 1) / 2 + kInvTop) * T.cw;
-    if (!addb && (!k->rowio || !k->add_classical)) T.Lc.fill(SL_C0, k->c_R2n2);
-    Mpz cfac;
-    const bool shifted = offset && offset_words > 0;
-    if (shifted) {
-        mpz_from_words(cfac, offset, offset_words);
-        mpz_mul(cfac, cfac, k->n); mpz_add_ui(cfac, cfac, 1); mpz_mod(cfac, cfac, k->n2);
-    }
+    if (!addb && !k->d_mul192 && (!k->rowio || !k->add_classical)) T.Lc.fill(SL_C0, k->c_R2n2);
     uint32_t *tops = (uint32_t *)c->inv_top.p;
     for (size_t j = 0; j < nch; j++) {
         const size_t off = j * chunk, m = std::min(chunk, count - off);

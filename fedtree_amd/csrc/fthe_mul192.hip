@@ -21,6 +21,7 @@
 // fthe_gprod192, below it, is the gathered 8-way product on the same routines: steps 2 and 3 per member with the
 // remainder kept in LDS as the next multiplier, steps 1 and 4 once per group.  fthe_pow192, the third
 // kernel, walks a whole exponent that way: x^e t by sliding windows over a table of odd powers.
+// fthe_inv192_up and fthe_inv192_down, the last two, are one level of a radix-8 batched inverse.
 #include <algorithm>
 #include <utility>
 
@@ -491,7 +492,186 @@ __global__ __launch_bounds__(64 * kWaves) void fthe_pow192_kernel(const uint32_t
     }
 }
 
+// fthe_inv192_up / fthe_inv192_down: one level of the radix-8 tree of Montgomery's trick, the batched inverse behind
+// fthe_invert and fthe_sub_inv (tools/mul192_model.py inverse()).  The geometry above; an octet owns
+// group g, the rows [8 g, 8 g + 8) of a level of `count` rows x (a row past the level's end: the integer 1), and walks
+// it with the running value resident in LDS as the multiplier column.  Level rows are canonical rows of 192 words;
+// what a group keeps for itself are lazy limb rows in fthe_pow192's entry format, which a lane reads back as it wrote
+// them.  Every product has factors below 2^6145: fthe_pow192's case, the same cut points.
+//
+//   up:    p_0 = x_0 -> the column and prefix entry 0; steps j = 1 .. 7: p_j = p_(j-1) x_j, x_j through the staging
+//          words, p_j -> prefix entry j (j < 7); the total p_7 -> step 4 -> row g of the level above.
+//   down:  R_7 = row g of the level above, inverted: the inverse of p_7 -> the column.  For j = 7 .. 1:
+//            A  the column R_j is parked in the octet's slot entry (the product consumes it; neither 29 more registers
+//               nor a second LDS area are to be had), I_j = R_j p_(j-1), the prefix entry in the registers;
+//            T  with a: I_j a_j, a_j through the staging words;
+//            B  x_j is staged over the spent high limbs, then step 4 and the store of row 8 g + j of out, then the
+//               column is R_j again from the slot and R_(j-1) = R_j x_j.
+//          I_0 = R_0 (T with a), step 4, row 8 g.  Row 8 g + j of x and of a is read before row 8 g + j of out is
+//          stored, and row 8 g of x is not read at all (p_0 is its copy): out may be exactly x or a.  One product site;
+//          every condition on the step is uniform.
+// An idle octet of the last batch repeats the last group and stores nothing.
+__device__ inline uint4 *prefix_at(uint32_t *pre, uint64_t g, uint32_t j, int l) {
+    return (uint4 *)(pre + (g * (kGather - 1) + j) * kEntryWords + 32 * opaque(l));
+}
+__device__ inline void column_from(uint32_t *area, int l, const uint32_t (&xl)[kPerLane]) {
+    uint32_t *a = area + kPerLane * opaque(l);
+#pragma unroll
+    for (int i = 0; i < kPerLane; i++) a[i] = xl[i];
+}
+__device__ inline void store_row(uint32_t *out, uint64_t row, int l, const uint32_t (&r)[24]) {
+    uint4 *p = (uint4 *)(out + row * kWords + 24 * l);
+#pragma unroll
+    for (int k = 0; k < 6; k++) p[k] = make_uint4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+}
+
+__global__ __launch_bounds__(64 * kWaves) void fthe_inv192_up_kernel(const uint32_t *x, uint32_t *pre, uint32_t *dst,
+                                                                     const uint32_t *kctx, uint64_t count, uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint64_t groups = (count + kGather - 1) / kGather, nbatch = (groups + kRowsPerWave - 1) / kRowsPerWave;
+    for (;;) {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&s_next, 1u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        const uint64_t batch = blockIdx.x + (uint64_t)t * nwg;
+        if (batch >= nbatch) break;
+        uint64_t g = batch * kRowsPerWave + oct;
+        const bool live = g < groups;
+        if (!live) g = groups - 1;
+        uint4 v[6];
+        uint32_t xl[kPerLane];
+        load_row(x, g * kGather, l, v);
+        stage(area, v, l);
+        wave_sync();
+        limbs_of(area, l, xl);
+        column_from(area, l, xl);
+        wave_sync();
+        if (live) entry_store(prefix_at(pre, g, 0, l), area, l);
+#pragma unroll 1
+        for (int j = 1; j < kGather; j++) {
+            const uint64_t row = g * kGather + j;
+            load_row(row < count ? x : nullptr, row, l, v);
+            stage(area, v, l);                 // over the spent high limbs of the step before
+            wave_sync();
+            limbs_of(area, l, xl);
+            wave_sync();
+            product<kFull>(xl, area, area, lane0, top);                 // z = x_j p_(j-1)
+            barrett(xl, area, s_mu, s_nl, l, lane0, top);
+            if (live && j < kGather - 1) entry_store(prefix_at(pre, g, j, l), area, l);
+        }
+        uint32_t r[24];
+        canonical_dwords(area, s_nd, l, lane0, r);
+        if (live) store_row(dst, g, l, r);
+        wave_sync();
+    }
+}
+
+__global__ __launch_bounds__(64 * kWaves) void fthe_inv192_down_kernel(const uint32_t *x, const uint32_t *a,
+                                                                       const uint32_t *inv, uint32_t *pre, uint32_t *park,
+                                                                       uint32_t *out, const uint32_t *kctx, uint64_t count,
+                                                                       uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint32_t slot0 = __builtin_amdgcn_readfirstlane((blockIdx.x * kWaves + wave) * kRowsPerWave);
+    const uint64_t groups = (count + kGather - 1) / kGather, nbatch = (groups + kRowsPerWave - 1) / kRowsPerWave;
+    const uint32_t per = a ? 3 : 2, total = (kGather - 1) * per + (a ? 1 : 0);
+    for (;;) {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&s_next, 1u);
+        t = __builtin_amdgcn_readfirstlane(t);
+        const uint64_t batch = blockIdx.x + (uint64_t)t * nwg;
+        if (batch >= nbatch) break;
+        // the octet's group, recomputed where it is used rather than kept across the products
+        auto group_of = [&](bool &live) {
+            const uint64_t g = batch * kRowsPerWave + (uint32_t)(opaque(lane) >> 3);
+            live = g < groups;
+            return live ? g : groups - 1;
+        };
+        uint32_t xl[kPerLane];
+        {
+            bool live;
+            uint4 v[6];
+            load_row(inv, group_of(live), l, v);
+            stage(area, v, l);
+            wave_sync();
+            limbs_of(area, l, xl);
+            column_from(area, l, xl);                                   // R_7
+        }
+#pragma unroll 1
+        for (uint32_t s = 0; s < total; s++) {
+            const uint32_t j = (kGather - 1) - s / per, ph = s - (kGather - 1 - j) * per;
+            bool live;
+            const uint64_t g = group_of(live), row = g * kGather + j;
+            wave_sync();
+            if (j && ph == 0) {                                         // A
+                uint4 *slot = entry_at(park, slot0, 1, 0, lane);
+                entry_store(slot, area, l);
+                entry_load(prefix_at(pre, g, j - 1, l), xl);
+            } else {
+                uint4 v[6];
+                const bool tail = !j || ph + 1 < per;                   // T, else B
+                load_row(row < count ? (tail ? a : x) : nullptr, row, l, v);
+                stage(area, v, l);                 // over the spent high limbs of the step before
+                if (!tail) {
+                    uint32_t r[24];
+                    canonical_dwords(area, s_nd, l, lane0, r);
+                    if (live && row < count) store_row(out, row, l, r);
+                    entry_load(entry_at(park, slot0, 1, 0, lane), xl);
+                    wave_sync();
+                    column_from(area, l, xl);                           // R_j again
+                }
+                wave_sync();
+                limbs_of(area, l, xl);
+            }
+            wave_sync();
+            product<kFull>(xl, area, area, lane0, top);
+            barrett(xl, area, s_mu, s_nl, l, lane0, top);
+        }
+        uint32_t r[24];
+        canonical_dwords(area, s_nd, l, lane0, r);
+        bool live;
+        const uint64_t g = group_of(live);
+        if (live) store_row(out, g * kGather, l, r);
+        wave_sync();
+    }
+}
+
 }  // namespace
+
+int launch_inv_up(hipStream_t st, const uint32_t *x, uint32_t *pre, uint32_t *dst, const void *kctx, size_t count,
+                  int n_cu) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = inv_blocks(count, n_cu);
+    hipLaunchKernelGGL(fthe_inv192_up_kernel, dim3(blocks), dim3(64 * kWaves), 0, st, x, pre, dst, (const uint32_t *)kctx,
+                       (uint64_t)count, blocks);
+    return hipGetLastError();
+}
+
+int launch_inv_down(hipStream_t st, const uint32_t *x, const uint32_t *a, const uint32_t *inv, uint32_t *pre,
+                    uint32_t *park, uint32_t *out, const void *kctx, size_t count, int n_cu) {
+    if (count == 0) return hipSuccess;
+    const unsigned blocks = inv_blocks(count, n_cu);
+    hipLaunchKernelGGL(fthe_inv192_down_kernel, dim3(blocks), dim3(64 * kWaves), 0, st, x, a, inv, pre, park, out,
+                       (const uint32_t *)kctx, (uint64_t)count, blocks);
+    return hipGetLastError();
+}
 
 int launch_pow(hipStream_t st, const uint32_t *x, int xw, const uint32_t *t, uint32_t *out, const void *kctx,
                const uint32_t *sched, uint32_t slen, unsigned entries, uint64_t products, uint32_t *table, int w,

@@ -124,4 +124,51 @@ int launch_pow(hipStream_t st, const uint32_t *x, int xw, const uint32_t *t, uin
                const uint32_t *sched, uint32_t slen, unsigned entries, uint64_t products, uint32_t *table, int w,
                size_t count, int n_cu);
 
+// ---- fthe_inv192_up / fthe_inv192_down: the batched inverse as a radix-8 tree ----
+// Level 0 is the call's count rows; level l + 1 has one row per group of 8 rows of level l, the group's product; the
+// first level of at most 8 rows is the top, inverted on the host.  Restates tools/mul192_model.py inverse_levels() /
+// inverse_products() / inverse_ws_bytes() exactly.
+constexpr size_t kInvRadix = 8;
+inline std::vector<size_t> inv_levels(size_t count) {
+    std::vector<size_t> ms(1, count);
+    while (ms.back() > kInvRadix) ms.push_back((ms.back() + kInvRadix - 1) / kInvRadix);
+    return ms;
+}
+// products as the kernels run them: per level below the top 7 per group up and 14 down, 8 more per group of level 0
+// for a; a tree that is the top alone multiplies its rows by a on fthe_mul192
+inline uint64_t inv_products(size_t count, bool with_a) {
+    const std::vector<size_t> ms = inv_levels(count);
+    if (ms.size() == 1) return with_a ? count : 0;
+    uint64_t p = with_a ? 8 * (uint64_t)ms[1] : 0;
+    for (size_t l = 1; l < ms.size(); l++) p += 21 * (uint64_t)ms[l];
+    return p;
+}
+// workgroups of a level's launch, one per CU at most; count <= 8: no launch
+inline unsigned inv_blocks(size_t count, int n_cu) {
+    if (count <= kInvRadix) return 0;
+    const size_t cu = (size_t)(n_cu > 1 ? n_cu : 1), groups = (count + kInvRadix - 1) / kInvRadix,
+                 wg = (groups + kPerWg - 1) / kPerWg;
+    return (unsigned)(wg < cu ? wg : cu);
+}
+// the workspace of one tree over count rows, blocks = inv_blocks(count, n_cu): the rows of the levels above level 0
+// (768 B each; count <= 8: the top's own rows), 7 prefix entries of 1,024 B per group of every level below the top,
+// one parking entry per slot (workgroup, wave, octet)
+inline size_t inv_ws_bytes(size_t count, unsigned blocks) {
+    const std::vector<size_t> ms = inv_levels(count);
+    size_t rows = ms.size() == 1 ? count : 0, groups = 0;
+    for (size_t l = 1; l < ms.size(); l++) { rows += ms[l]; groups += ms[l]; }
+    return rows * kWords * 4 + groups * (kInvRadix - 1) * kEntryWords * 4 + (size_t)blocks * kPerWg * kEntryWords * 4;
+}
+
+// One level up: dst[g] = prod_{j < 8} x[8 g + j] mod N for the ceil(count / 8) groups of the level's count rows (a row
+// past the end: 1), canonical rows; pre receives the groups' 7 prefix entries (entry 7 g + j: x[8 g] ... x[8 g + j],
+// lazy limb rows).  dst and pre must not overlap x.  Returns a hipError_t.
+int launch_inv_up(hipStream_t st, const uint32_t *x, uint32_t *pre, uint32_t *dst, const void *kctx, size_t count,
+                  int n_cu);
+// One level down: out[8 g + j] = inv[g] prod_{i != j} x[8 g + i] (times a[8 g + j] unless a is null), canonical rows,
+// with pre as launch_inv_up left it for x and inv[g] the inverse of dst[g]; park: inv_blocks(count, n_cu) x 64 entries.
+// out may be exactly x or a.  Returns a hipError_t.
+int launch_inv_down(hipStream_t st, const uint32_t *x, const uint32_t *a, const uint32_t *inv, uint32_t *pre,
+                    uint32_t *park, uint32_t *out, const void *kctx, size_t count, int n_cu);
+
 }  // namespace mul192

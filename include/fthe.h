@@ -116,9 +116,30 @@ void  fthe_host_free(void *p);
  *     fthe_reduce_segments[_dev], fthe_reduce_segments_csr_dev, fthe_reduce_segments_zero_first_dev,
  *     fthe_histogram_dev, fthe_histogram_zero_first_dev, fthe_scan_segments[_dev]
  * with the same rows in and out; a pass whose out overlaps its source rows keeps that pass's rows in the context's
- * scratch, under the same limit.  fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.
+ * scratch, under the same limit.  Negation and subtraction at this size are the batched inverse,
+ *     fthe_invert[_dev], fthe_sub_inv[_dev]
+ * with the contract of the other sizes: 3 products per row for fthe_invert, 4 for fthe_sub_inv, no private key;
+ * count == 0 is FTHE_OK, offset_words of 0..n_words, out may be exactly x, a or b, and one row that is no unit mod
+ * n^2 fails the whole call with FTHE_ERR_ARG before anything is written to out; rows >= n^2 are accepted and
+ * inverted as their residues.  A tree covers a chunk of min(count, 2^20) rows (FTHE_INV_CHUNK); a call of several
+ * chunks runs every chunk's up-sweep and host inversion first, then each up-sweep again with its down-sweep.  The
+ * host forms stage their rows whole through the context's buffers.  By default the tree is the binary one of the
+ * other sizes with its products on fthe_mul192: its workspace in the context's scratch is two rows of 768 B per row
+ * of the chunk, and under fthe_ctx_set_mem_limit the chunk shrinks to what fits (FTHE_ERR_NOMEM below one row's).
+ * FTHE_INV192_TREE=0 (read per call) runs the same inverse, byte-identical, on two more kernels of that file
+ * (fthe_inv192_up / fthe_inv192_down: a tree of groups of 8 rows, a group's running product resident in LDS); they
+ * measured slower than the binary tree at every size tried and are kept as the A/B arm.  Their
+ * workspace for a chunk of m rows: with the levels m_0 = m, m_(l+1) = ceil(m_l / 8) down to the first of at most 8
+ * rows, and S the sum of m_1 .. m_t,
+ *     S x 768 B (the level rows) + S x 7 x 1024 B (the groups' prefix products)
+ *     + min(ceil(ceil(m / 8) / 64), CUs) x 64 x 1024 B (one parked row per octet of the launch),
+ * about 1.0 KB per row (m <= 8: m x 768 B and nothing else; mul192::inv_ws_bytes), the chunk shrinking under the
+ * limit to the most rows whose workspace fits.  fthe_sub and fthe_sub_bits stay FTHE_ERR_UNSUPPORTED: they raise
+ * the subtrahend to 2^bits - 1, about 80 products per row against 4, and leave its residue in the plaintext;
+ * subtraction at this size is fthe_sub_inv with a public offset that keeps the plaintext non-negative.
+ * fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.
  * Every other call that works mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits,
- * fthe_invert, fthe_sub_inv, fthe_scalar_mul_rows, fthe_dot_segments, the
+ * fthe_scalar_mul_rows, fthe_dot_segments, the
  * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the packed and slot-packed pair
  * calls, the public-key encrypt with a fixed-base flag, and fthe_add_shared / fthe_scalar_mul_u64_shared /
  * fthe_encrypt_shared on the public path.  A key holder's CRT encrypt

@@ -22,7 +22,9 @@ kernel forms r modulo 2^(27 * 228) (2N < 2^6145), limb by limb in the borrow cha
 borrow or when that bit (limb 227, bit 15) is set.
 
 chain() is the gathered product of fthe_gprod192 (one lazy factor per product), power() the sliding-window walk of
-fthe_pow192 (both factors lazy) with its schedule builder: schedule(), products(), plan().
+fthe_pow192 (both factors lazy) with its schedule builder: schedule(), products(), plan().  inverse() is the radix-8
+tree of fthe_inv192_up / fthe_inv192_down with its count and workspace formulas: inverse_levels(),
+inverse_products(), inverse_blocks(), inverse_ws_bytes().
 
 Run:  python tools/mul192_model.py [seed] [trials]
 """
@@ -219,6 +221,147 @@ def plan(e, tail=False, wmax=MAX_WINDOW):
     return min(((w, schedule(e, w)) for w in range(1, wmax + 1)), key=lambda p: (products(p[1], tail), p[0]))
 
 
+def lazy_product(xl, r, N, lanes=False, ran=None):
+    """registers xl times the multiplier column r, both below 2^6145 -> the lazy remainder in [0, 2N): one product of
+    fthe_pow192 and of the inverse kernels, every bound of power()'s docstring asserted.  ran[0] counts the calls."""
+    prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
+    mu = mu_of(N)
+    assert xl < 1 << 6145 and r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
+    z = prod(xl, r)
+    assert z == xl * r and z < 1 << 12290
+    z1 = z >> (B * SHIFT_A)
+    assert z1 < 1 << (B * SHIFT_B)
+    zm = prod(z1, mu)
+    assert zm < 1 << (B * 2 * LIMBS)
+    q = zm >> (B * SHIFT_B)
+    assert q < 1 << (B * 230) and z // N - 1 <= q <= z // N
+    if lanes:
+        low = ring(limbs(q), limbs(N), drain=False)
+        zl, rl, borrow = limbs(z, 2 * LIMBS), [], 0
+        for s in range(LIMBS):
+            d = (zl[s] - low[s] - borrow) & 0xFFFFFFFF
+            borrow = d >> 31
+            rl.append(d & MASK if s < R_LIMBS else 0)
+        out = value(rl)
+    else:
+        out = (z - q * N) % (1 << (B * R_LIMBS))
+    assert out == z - q * N and 0 <= out < 2 * N
+    if ran is not None:
+        ran[0] += 1
+    return out
+
+
+def canonical(r, N):
+    """step 4: a lazy remainder in [0, 2N) -> the row in [0, N)"""
+    row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
+    assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
+    if high or row >= N:
+        row = (row - N) % (1 << (32 * WORDS))
+    assert row == r % N
+    return row
+
+
+RADIX = 8
+ENTRY_BYTES = 32 * LANES * 4        # a lazy limb row: each lane's 29 limbs padded to 32 words
+PER_WG = 64                         # rows (here: groups) of a workgroup's eight waves
+
+
+def inverse_levels(count):
+    """rows of level 0 .. t of the radix-8 tree: a row per group of 8 of the level below, down to at most 8 rows"""
+    ms = [count]
+    while ms[-1] > RADIX:
+        ms.append(-(-ms[-1] // RADIX))
+    return ms
+
+
+def inverse_products(count, with_a):
+    """products as the kernels run them (fthe_last_montmuls): per level below the top 7 per group up and 14 down, 8
+    more per group of level 0 for a; a tree that is the top alone multiplies its rows by a on fthe_mul192"""
+    ms = inverse_levels(count)
+    if len(ms) == 1:
+        return count if with_a else 0
+    return 21 * sum(ms[1:]) + (8 * ms[1] if with_a else 0)
+
+
+def inverse_blocks(count, n_cu):
+    """workgroups of the level-0 launches, one per CU at most; none when the tree is the top alone"""
+    return 0 if count <= RADIX else min(-(-(-(-count // RADIX)) // PER_WG), max(n_cu, 1))
+
+
+def inverse_ws_bytes(count, blocks):
+    """workspace of one tree: the rows of the levels above level 0 (the top's own rows when it stands alone), 7 prefix
+    entries per group of every level below the top, a parking entry per slot (workgroup, wave, octet)"""
+    ms = inverse_levels(count)
+    rows = count if len(ms) == 1 else sum(ms[1:])
+    return rows * WORDS * 4 + sum(ms[1:]) * (RADIX - 1) * ENTRY_BYTES + blocks * PER_WG * ENTRY_BYTES
+
+
+def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None):
+    """[a_i x_i^-1 (1 + offset n) mod N] (a None: 1) as fthe_inv192_up / fthe_inv192_down form it, N =
+    n^2 (n None: its root), xs any rows of 192 words that are units mod N.  Groups of eight consecutive rows of a level,
+    a short last group filled up with 1; the level above holds the groups' products as canonical rows; the first level
+    of at most 8 rows is inverted on Python's integers as the host does it; going down, group g turns R_7 = row g of
+    the level above into I_j = R_j p_(j-1) (times a_j at level 0) and R_(j-1) = R_j x_j for j = 7 .. 1, I_0 = R_0.
+    Every product goes through lazy_product(), which asserts power()'s bounds.  count: a list that receives the
+    number of products run.  Returns the canonical rows."""
+    from math import isqrt
+    n = isqrt(N) if n is None else n
+    assert n_ok(n) and n * n == N and all(0 <= v < 1 << (32 * WORDS) for v in list(xs) + list(a or []))
+    ran = [0]
+
+    def step(xl, r):
+        return lazy_product(xl, r, N, lanes, ran)
+
+    ms = inverse_levels(len(xs))
+    levels, prefixes = [list(xs)], []
+    for m in ms[1:]:                                      # up
+        src, pre, tot = levels[-1], [], []
+        for g in range(m):
+            x = (src[RADIX * g:RADIX * g + RADIX] + [1] * RADIX)[:RADIX]
+            p = [x[0]]
+            for j in range(1, RADIX):
+                p.append(step(x[j], p[-1]))
+            pre.append(p[:RADIX - 1])
+            tot.append(canonical(p[-1], N))
+        prefixes.append(pre)
+        levels.append(tot)
+    top = [v % N for v in levels[-1]]                     # the host: prefix products, one inversion, walk back
+    inv = pow(reduce_mod(top, N), -1, N) * (1 + offset * n) % N
+    invs = [0] * len(top)
+    for j in reversed(range(len(top))):
+        invs[j] = inv * reduce_mod(top[:j], N) % N
+        inv = inv * top[j] % N
+    if len(ms) == 1 and a is not None:
+        invs = [canonical(step(a[i], invs[i]), N) for i in range(len(xs))]
+    for l in reversed(range(len(ms) - 1)):                # down
+        src, out = levels[l], [None] * ms[l]
+        for g in range(ms[l + 1]):
+            x = (src[RADIX * g:RADIX * g + RADIX] + [1] * RADIX)[:RADIX]
+            r = invs[g]
+            for j in reversed(range(RADIX)):
+                i = step(prefixes[l][g][j - 1], r) if j else r
+                if l == 0 and a is not None:
+                    i = step(a[RADIX * g + j] if RADIX * g + j < ms[l] else 1, i)
+                if RADIX * g + j < ms[l]:
+                    out[RADIX * g + j] = canonical(i, N)
+                if j:
+                    r = step(x[j], r)
+        invs = out
+    assert ran[0] == inverse_products(len(xs), a is not None)
+    if count is not None:
+        count.append(ran[0])
+    for i, v in enumerate(invs):
+        assert v == (1 if a is None else a[i]) * pow(xs[i], -1, N) * (1 + offset * n) % N
+    return invs
+
+
+def reduce_mod(vs, N):
+    r = 1
+    for v in vs:
+        r = r * v % N
+    return r
+
+
 def power(x, e, n, t=None, w=None, lanes=False, count=None):
     """x^e t mod n^2 as fthe_pow192 forms it, e >= 2, x any row of at most 192 words, t any row or None
     (the integer 1); w: the window width, None for plan()'s.  Every product multiplies registers xl by the multiplier
@@ -233,34 +376,10 @@ def power(x, e, n, t=None, w=None, lanes=False, count=None):
     number of products run.  Returns the canonical result."""
     assert n_ok(n) and e >= 2 and 0 <= x < 1 << (32 * WORDS) and (t is None or 0 <= t < 1 << (32 * WORDS))
     N = n * n
-    mu = mu_of(N)
-    prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
     ran = [0]
 
     def step(xl, r):
-        """registers xl times the multiplier column r -> the lazy remainder"""
-        assert xl < 1 << 6145 and r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
-        z = prod(xl, r)
-        assert z == xl * r and z < 1 << 12290
-        z1 = z >> (B * SHIFT_A)
-        assert z1 < 1 << (B * SHIFT_B)
-        zm = prod(z1, mu)
-        assert zm < 1 << (B * 2 * LIMBS)
-        q = zm >> (B * SHIFT_B)
-        assert q < 1 << (B * 230) and z // N - 1 <= q <= z // N
-        if lanes:
-            low = ring(limbs(q), limbs(N), drain=False)
-            zl, rl, borrow = limbs(z, 2 * LIMBS), [], 0
-            for s in range(LIMBS):
-                d = (zl[s] - low[s] - borrow) & 0xFFFFFFFF
-                borrow = d >> 31
-                rl.append(d & MASK if s < R_LIMBS else 0)
-            out = value(rl)
-        else:
-            out = (z - q * N) % (1 << (B * R_LIMBS))
-        assert out == z - q * N and 0 <= out < 2 * N
-        ran[0] += 1
-        return out
+        return lazy_product(xl, r, N, lanes, ran)
 
     sched = schedule(e, w) if w else plan(e, t is not None)[1]
     entries = max(sched)
@@ -300,6 +419,8 @@ def main():
         chain([top] * 3 + [rng.getrandbits(32 * WORDS) for _ in range(5)], n, lanes=trials <= 4)
         power(top, n, n, t=top)
         power(rng.getrandbits(32 * WORDS), rng.getrandbits(12) | 2, n, w=3, lanes=trials <= 4)
+        N = n * n
+        inverse(N, [top // N * N - 1, N - 1, 2, 1] * 3, a=[top] * 12, offset=1, n=n)
     print("mul192 model: ok")
 
 
