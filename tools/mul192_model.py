@@ -135,7 +135,7 @@ def mul(x, y, n, lanes=False):
     return r
 
 
-def chain(rows, n, lanes=False):
+def chain(rows, n, lanes=False, observer=None):
     """prod(rows) mod n^2 as fthe_gprod192 forms it: the first row is the multiplier column, every
     further row x gives z = x r and the lazy remainder r = z - q N in [0, 2N), which stays in limbs as the next
     multiplier; only the last r is made canonical.  Fewer than two rows are filled up with the integer 1, so there is
@@ -145,7 +145,8 @@ def chain(rows, n, lanes=False):
         q  = floor(z1 mu/2^b) <= z / N < 2^6209            230 limbs (below 2^6210)
         z1 mu / 2^b > z / N - z / 2^(a+b) - 2^a / N > z / N - 2^-23 - 2^-5
     so q is still floor(z / N) or one below it, and r < 2N < 2^(27 * 228) with limbs 228..231 zero.  Every bound is
-    asserted.  lanes: the three products of every step through ring() (slow)."""
+    asserted.  lanes: the three products of every step through ring() (slow).  observer: as lazy_product()'s and
+    canonical()'s."""
     assert n_ok(n) and all(0 <= x < 1 << (32 * WORDS) for x in rows)
     N = n * n
     mu = mu_of(N)
@@ -154,6 +155,7 @@ def chain(rows, n, lanes=False):
     r = rows[0]
     for x in rows[1:]:
         assert r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
+        col = r
         z = prod(x, r)
         assert z == x * r and z < 1 << 12289
         z1 = z >> (B * SHIFT_A)
@@ -173,6 +175,10 @@ def chain(rows, n, lanes=False):
         else:
             r = (z - q * N) % (1 << (B * R_LIMBS))
         assert r == z - q * N and 0 <= r < 2 * N
+        if observer is not None:
+            observer("product", x, col, r, q == z // N)
+    if observer is not None:
+        observer("canonical", r)
     row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
     assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
     if high or row >= N:
@@ -221,9 +227,12 @@ def plan(e, tail=False, wmax=MAX_WINDOW):
     return min(((w, schedule(e, w)) for w in range(1, wmax + 1)), key=lambda p: (products(p[1], tail), p[0]))
 
 
-def lazy_product(xl, r, N, lanes=False, ran=None):
+def lazy_product(xl, r, N, lanes=False, ran=None, observer=None):
     """registers xl times the multiplier column r, both below 2^6145 -> the lazy remainder in [0, 2N): one product of
-    fthe_pow192 and of the inverse kernels, every bound of power()'s docstring asserted.  ran[0] counts the calls."""
+    fthe_pow192 and of the inverse kernels, every bound of power()'s docstring asserted.  ran[0] counts the calls.
+    observer: called as observer("product", xl, r, out, exact) after every product, exact telling whether the
+    quotient was floor(z / N) (out < N) or one below it; canonical() calls it as observer("canonical", r) and
+    inverse() as observer("phase", name) where a sweep begins.  It changes no result."""
     prod = (lambda a, b: value(ring(limbs(a), limbs(b)))) if lanes else (lambda a, b: a * b)
     mu = mu_of(N)
     assert xl < 1 << 6145 and r < 1 << 6145 and limbs(r)[R_LIMBS:] == [0] * (LIMBS - R_LIMBS)
@@ -248,11 +257,15 @@ def lazy_product(xl, r, N, lanes=False, ran=None):
     assert out == z - q * N and 0 <= out < 2 * N
     if ran is not None:
         ran[0] += 1
+    if observer is not None:
+        observer("product", xl, r, out, q == z // N)
     return out
 
 
-def canonical(r, N):
+def canonical(r, N, observer=None):
     """step 4: a lazy remainder in [0, 2N) -> the row in [0, N)"""
+    if observer is not None:
+        observer("canonical", r)
     row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
     assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
     if high or row >= N:
@@ -296,23 +309,32 @@ def inverse_ws_bytes(count, blocks):
     return rows * WORDS * 4 + sum(ms[1:]) * (RADIX - 1) * ENTRY_BYTES + blocks * PER_WG * ENTRY_BYTES
 
 
-def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None):
+def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None, observer=None):
     """[a_i x_i^-1 (1 + offset n) mod N] (a None: 1) as fthe_inv192_up / fthe_inv192_down form it, N =
     n^2 (n None: its root), xs any rows of 192 words that are units mod N.  Groups of eight consecutive rows of a level,
     a short last group filled up with 1; the level above holds the groups' products as canonical rows; the first level
     of at most 8 rows is inverted on Python's integers as the host does it; going down, group g turns R_7 = row g of
     the level above into I_j = R_j p_(j-1) (times a_j at level 0) and R_(j-1) = R_j x_j for j = 7 .. 1, I_0 = R_0.
     Every product goes through lazy_product(), which asserts power()'s bounds.  count: a list that receives the
-    number of products run.  Returns the canonical rows."""
+    number of products run.  observer: lazy_product()'s, told "up", "top" (a tree that is the top alone: its products by a
+    on fthe_mul192) and "down" as phases.  Returns the canonical rows."""
     from math import isqrt
     n = isqrt(N) if n is None else n
     assert n_ok(n) and n * n == N and all(0 <= v < 1 << (32 * WORDS) for v in list(xs) + list(a or []))
     ran = [0]
 
     def step(xl, r):
-        return lazy_product(xl, r, N, lanes, ran)
+        return lazy_product(xl, r, N, lanes, ran, observer)
+
+    def canon(r):
+        return canonical(r, N, observer)
+
+    def phase(name):
+        if observer is not None:
+            observer("phase", name)
 
     ms = inverse_levels(len(xs))
+    phase("up")
     levels, prefixes = [list(xs)], []
     for m in ms[1:]:                                      # up
         src, pre, tot = levels[-1], [], []
@@ -322,7 +344,7 @@ def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None):
             for j in range(1, RADIX):
                 p.append(step(x[j], p[-1]))
             pre.append(p[:RADIX - 1])
-            tot.append(canonical(p[-1], N))
+            tot.append(canon(p[-1]))
         prefixes.append(pre)
         levels.append(tot)
     top = [v % N for v in levels[-1]]                     # the host: prefix products, one inversion, walk back
@@ -332,7 +354,9 @@ def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None):
         invs[j] = inv * reduce_mod(top[:j], N) % N
         inv = inv * top[j] % N
     if len(ms) == 1 and a is not None:
-        invs = [canonical(step(a[i], invs[i]), N) for i in range(len(xs))]
+        phase("top")
+        invs = [canon(step(a[i], invs[i])) for i in range(len(xs))]
+    phase("down")
     for l in reversed(range(len(ms) - 1)):                # down
         src, out = levels[l], [None] * ms[l]
         for g in range(ms[l + 1]):
@@ -343,7 +367,7 @@ def inverse(N, xs, a=None, offset=0, n=None, lanes=False, count=None):
                 if l == 0 and a is not None:
                     i = step(a[RADIX * g + j] if RADIX * g + j < ms[l] else 1, i)
                 if RADIX * g + j < ms[l]:
-                    out[RADIX * g + j] = canonical(i, N)
+                    out[RADIX * g + j] = canon(i)
                 if j:
                     r = step(x[j], r)
         invs = out
@@ -362,7 +386,7 @@ def reduce_mod(vs, N):
     return r
 
 
-def power(x, e, n, t=None, w=None, lanes=False, count=None):
+def power(x, e, n, t=None, w=None, lanes=False, count=None, observer=None):
     """x^e t mod n^2 as fthe_pow192 forms it, e >= 2, x any row of at most 192 words, t any row or None
     (the integer 1); w: the window width, None for plan()'s.  Every product multiplies registers xl by the multiplier
     column r, and from the second product on both are lazy remainders below 2N <= 2^6145:
@@ -373,13 +397,13 @@ def power(x, e, n, t=None, w=None, lanes=False, count=None):
         z1 mu / 2^b > z / N - z / 2^(a+b) - 2^a / N > z / N - 2^-22 - 2^-5
     so q is floor(z / N) or one below it and r = z - q N stays in [0, 2N) with limbs 228..231 zero.  Each bound, and
     ring()'s column sum below 2^62 where lanes is set, is asserted at every product.  count: a list that receives the
-    number of products run.  Returns the canonical result."""
+    number of products run.  observer: lazy_product()'s.  Returns the canonical result."""
     assert n_ok(n) and e >= 2 and 0 <= x < 1 << (32 * WORDS) and (t is None or 0 <= t < 1 << (32 * WORDS))
     N = n * n
     ran = [0]
 
     def step(xl, r):
-        return lazy_product(xl, r, N, lanes, ran)
+        return lazy_product(xl, r, N, lanes, ran, observer)
 
     sched = schedule(e, w) if w else plan(e, t is not None)[1]
     entries = max(sched)
@@ -398,10 +422,7 @@ def power(x, e, n, t=None, w=None, lanes=False, count=None):
     assert ran[0] == products(sched, t is not None)
     if count is not None:
         count.append(ran[0])
-    row, high = r % (1 << (32 * WORDS)), r >> (32 * WORDS)
-    assert high == limbs(r)[R_LIMBS - 1] >> (32 * WORDS % B)
-    if high or row >= N:
-        row = (row - N) % (1 << (32 * WORDS))
+    row = canonical(r, N, observer)
     assert row == pow(x, e, N) * (1 if t is None else t) % N
     return row
 
