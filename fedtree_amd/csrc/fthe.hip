@@ -3365,9 +3365,13 @@ extern "C" int fthe_decrypt_short_dev(fthe_key *k, fthe_ctx *c, const uint32_t *
 // ---------------------------------------------------------------------------
 // Packed gradient pairs: one ciphertext per (g, h) (include/fthe.h)
 static dim3 grid256(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
-// a 96-word n whose encrypt would take the public path (fthe_pow192): the packed and slot calls stay unsupported there
+// a 96-word n whose encrypt would take the public path: fthe_pow192 serves it unless a fixed-base flag is set; the
+// packed and slot encrypts reach it as general plaintexts (MsgSrc::mw), fthe_encrypt_shared stays unsupported there
 static bool pow192_only(const fthe_key *k, int flags) {
     return k->d_mul192 && (!k->priv || (flags & FTHE_ENC_PUBLIC));
+}
+static bool pow192_fenced(const fthe_key *k, int flags) {
+    return pow192_only(k, flags) && (flags & (FTHE_ENC_FIXED_BASE | FTHE_ENC_FIXED_BASE_EXACT));
 }
 
 extern "C" int fthe_pack_gh_dev(fthe_ctx *c, const float *g, const float *h, size_t count, uint32_t *m) {
@@ -3394,7 +3398,7 @@ static int encrypt_gh_impl(fthe_key *k, fthe_ctx *c, const float *g, const float
                            int r_words, uint64_t rng_seed, uint64_t index0, uint32_t *out, int flags, HostPipe *pipe) {
     if (!k || !c || ((!g || !h || !out) && count)) return FTHE_ERR_ARG;
     if (k->n_words < FTHE_GH_PACKED_WORDS) return FTHE_ERR_ARG;
-    if (pow192_only(k, flags)) return FTHE_ERR_UNSUPPORTED;
+    if (pow192_fenced(k, flags)) return FTHE_ERR_UNSUPPORTED;
     HIPOK(hipSetDevice(c->device));
     int rc = c->gh[0].ensure(std::max<size_t>(4, count * FTHE_GH_PACKED_WORDS * 4));
     if (rc) return rc;
@@ -3463,7 +3467,7 @@ extern "C" int fthe_unpack_gh_slots_dev(fthe_ctx *c, const uint32_t *m, int stri
 static int encrypt_gh_slots_impl(fthe_key *k, fthe_ctx *c, const float *g, const float *h, size_t count, int slot_bits,
                                  int slots, const uint32_t *r, int r_words, uint64_t rng_seed, uint32_t *out, int flags,
                                  HostPipe *pipe) {
-    if (pow192_only(k, flags)) return FTHE_ERR_UNSUPPORTED;
+    if (pow192_fenced(k, flags)) return FTHE_ERR_UNSUPPORTED;
     HIPOK(hipSetDevice(c->device));
     const size_t rows = (count + slots - 1) / slots;
     const int sw = slot_bits / 32, mww = slots * sw;
@@ -3507,6 +3511,13 @@ extern "C" int fthe_decrypt_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32_
     if (rc) return rc;
     return decrypt_gh_slots_impl(k, c, ct, count, slot_bits, slots, GhOut{g, h, g_code, h_code}, short_pt != 0, nullptr);
 }
+
+// Paillier-3072 (d_mul192): the same walk on fthe_horner192, defined with the other calls of that size below.
+static int mul192_begin(fthe_ctx *c, const fthe_key *k, size_t scratch = 0);
+static int mul192_end(fthe_ctx *c, double products);
+static int horner192(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t stride, size_t rows, int J, size_t nA, int sq,
+                     uint32_t *out);
+static double horner192_products(size_t rows, int J, size_t nA, int sq);
 
 // Compress: count pair-packed ciphertexts -> rows = ceil(count / slots) slot-packed ones,
 //     out[i] = prod_j x[j rows + i]^(2^(j slot_bits)) mod n^2,
@@ -3579,11 +3590,15 @@ extern "C" int fthe_compress_gh_slots_dev(fthe_key *k, fthe_ctx *c, const uint32
     if (!k || !c || ((!x || !out) && count)) return FTHE_ERR_ARG;
     int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
     if (rc) return rc;
-    if (!k->pub_ok) return FTHE_ERR_UNSUPPORTED;
+    if (!k->pub_ok && !k->d_mul192) return FTHE_ERR_UNSUPPORTED;
     if (!count) return FTHE_OK;
     const size_t rows = (count + slots - 1) / slots;
     const int J = (int)((count + rows - 1) / rows);          // planes of the first nA rows; J - 1 for the rest
     const size_t nA = count - (size_t)(J - 1) * rows;
+    if (k->d_mul192) {
+        if ((rc = mul192_begin(c, k)) || (rc = horner192(k, c, x, rows, rows, J, nA, slot_bits, out))) return rc;
+        return mul192_end(c, horner192_products(rows, J, nA, slot_bits));
+    }
     return horner_planes(k, c, x, rows, J, nA, slot_bits, out);
 }
 
@@ -3659,7 +3674,7 @@ static int mul192_scratch(fthe_ctx *c, size_t bytes) {
     if (c->mem_limit && bytes > c->mem_limit && bytes > c->scratch.n) return FTHE_ERR_NOMEM;
     return c->scratch.ensure(bytes);
 }
-static int mul192_begin(fthe_ctx *c, const fthe_key *k, size_t scratch = 0) {
+static int mul192_begin(fthe_ctx *c, const fthe_key *k, size_t scratch) {
     if (k->device != c->device) return FTHE_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     if (scratch)
@@ -3677,6 +3692,50 @@ static int mul192_end(fthe_ctx *c, double products) {
     Launch Lc;
     Lc.mm = products;
     return end_call(c, Lc);
+}
+// horner_planes on fthe_horner192 (fthe_mul192.hip): out[i] = prod_j x[j stride + i]^(2^(j sq)) for rows
+// [0, nA) with J planes and [nA, rows) with J - 1, a launch set per plane count so that no row squares the integer 1;
+// a lone plane is a copy.  out must not overlap x.  No scratch; the caller brackets it with mul192_begin / mul192_end.
+static int horner192(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t stride, size_t rows, int J, size_t nA, int sq,
+                     uint32_t *out) {
+    const size_t cw = mul192::kWords;
+    auto run = [&](size_t r0, size_t r1, int planes) -> int {
+        if (r1 <= r0 || planes < 1) return FTHE_OK;
+        if (planes == 1) {
+            HIPOK(hipMemcpyAsync(out + r0 * cw, x + r0 * cw, (r1 - r0) * cw * 4, hipMemcpyDeviceToDevice, c->stream));
+            return FTHE_OK;
+        }
+        return mul192::launch_horner(c->stream, x + r0 * cw, stride, planes, sq, out + r0 * cw, k->d_mul192, r1 - r0,
+                                     c->n_cu) == hipSuccess ? FTHE_OK : FTHE_ERR_HIP;
+    };
+    if (int rc = run(0, nA, J)) return rc;
+    return run(nA, rows, J - 1);
+}
+// the call's product count: 1 + (P - 1)(sq + 1) for a row of P planes (a copied row counts as its seed)
+static double horner192_products(size_t rows, int J, size_t nA, int sq) {
+    return (double)nA * (double)mul192::horner_products(J, sq) +
+           (double)(rows - nA) * (double)mul192::horner_products(std::max(J - 1, 1), sq);
+}
+// The host form: output rows in chunks of FTHE_MUL192_CHUNK, a chunk's planes staged side by side in io[0] (at most
+// chunk * J rows) and its rows drained from io[2], on the context's stream.
+static int horner192_host(fthe_key *k, fthe_ctx *c, const uint32_t *x, size_t rows, int J, size_t nA, int sq,
+                          uint32_t *out) {
+    const size_t L = std::min(mul192_chunk_rows(), rows), cw = mul192::kWords;
+    int rc;
+    if ((rc = c->io[0].ensure(L * J * cw * 4)) || (rc = c->io[2].ensure(L * cw * 4)) || (rc = mul192_begin(c, k))) return rc;
+    uint32_t *din = (uint32_t *)c->io[0].p, *dout = (uint32_t *)c->io[2].p;
+    for (size_t off = 0; off < rows; off += L) {
+        const size_t cnt = std::min(L, rows - off), a = std::min(cnt, nA > off ? nA - off : 0);
+        const int planes = a ? J : J - 1;                     // of the chunk's first rows; all of them when a == 0
+        for (int j = 0; j < planes; j++) {
+            const size_t n = j + 1 < planes || !a ? cnt : a;  // the top plane ends at row nA
+            HIPOK(hipMemcpyAsync(din + j * cnt * cw, x + (j * rows + off) * cw, n * cw * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        if ((rc = horner192(k, c, din, cnt, cnt, planes, a ? a : cnt, sq, dout))) return rc;
+        HIPOK(hipMemcpyAsync(out + off * cw, dout, cnt * cw * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPOK(hipStreamSynchronize(c->stream));               // io[0] is restaged by the next chunk
+    }
+    return mul192_end(c, horner192_products(rows, J, nA, sq));
 }
 // the add: device rows in one persistent launch; host rows (pipe) in chunks of the row-I/O add's footprint
 static int mul192_pair(fthe_key *k, fthe_ctx *c, const uint32_t *a, const uint32_t *b, size_t count, uint32_t *out,
@@ -5506,6 +5565,12 @@ extern "C" int fthe_compress_gh_slots(fthe_key *k, fthe_ctx *c, const uint32_t *
     int rc = gh_slots_of(k, slot_bits, 0, slots, &slots);
     if (rc) return rc;
     const size_t row = 2 * (size_t)k->n_words * 4, rows = (count + slots - 1) / slots;
+    if (k->d_mul192 && count) {                  // Paillier-3072: staged by chunks of output rows
+        if (k->device != c->device) return FTHE_ERR_ARG;
+        HIPOK(hipSetDevice(c->device));
+        const int J = (int)((count + rows - 1) / rows);
+        return horner192_host(k, c, x, rows, J, count - (size_t)(J - 1) * rows, slot_bits, out);
+    }
     return host_in_out(c, x, count * row, out, rows * row, [&](const uint32_t *dx, uint32_t *dout) {
         return fthe_compress_gh_slots_dev(k, c, dx, count, slot_bits, dout, slots);
     });

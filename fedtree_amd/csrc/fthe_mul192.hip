@@ -21,7 +21,8 @@
 // fthe_gprod192, below it, is the gathered 8-way product on the same routines: steps 2 and 3 per member with the
 // remainder kept in LDS as the next multiplier, steps 1 and 4 once per group.  fthe_pow192, the third
 // kernel, walks a whole exponent that way: x^e t by sliding windows over a table of odd powers.
-// fthe_inv192_up and fthe_inv192_down, the last two, are one level of a radix-8 batched inverse.
+// fthe_inv192_up and fthe_inv192_down are one level of a radix-8 batched inverse; fthe_horner192, the
+// last, is the Horner walk over planes of rows behind the slot compress.
 #include <algorithm>
 #include <utility>
 
@@ -653,7 +654,113 @@ __global__ __launch_bounds__(64 * kWaves) void fthe_inv192_down_kernel(const uin
     }
 }
 
+// fthe_horner192: out[i] = prod_{j < planes} x[j stride + i]^(2^(j sq)) mod N, the Horner walk behind the compress of
+// pair-packed into slot-packed ciphertexts (tools/mul192_model.py horner()).  planes >= 2 and sq >= 1
+// are the launch's: every wave runs the same 1 + (planes - 1)(sq + 1) products.  The geometry above; an octet owns
+// output row i for the whole walk, with the running value resident in LDS as the multiplier column:
+//
+//   seed: the top plane's row -> staging words -> limbs x in registers; one product by the column 1 and step 3 leave it
+//   as a lazy remainder in [0, 2N) in area[0, 228): fthe_pow192's base step.
+//   per plane below the top: sq squarings, the registers taking the column itself (column_of: nothing is re-limbed),
+//   then one product by that plane's row, loaded at that step and staged over the spent high limbs as fthe_pow192's
+//   tail stages t.  (Loading it one squaring ahead holds 24 registers across a product: 256 VGPRs and 8 spilled
+//   against 240 and none, for one row's latency per sq + 1 products.)
+//   Nothing is converted, subtracted or stored between products; both factors are below 2^6145, a staged row below
+//   2^6144: fthe_pow192's case, the same cut points.  After the last product only: step 4 and the store.
+//
+// One product site; every condition on the step is uniform.  A row of out is written by its octet alone, after every
+// row of x that the octet reads: out must not overlap x all the same, since other octets read other planes of the
+// same rows later.  An idle octet of the last batch repeats the last row and stores nothing.
+__global__ __launch_bounds__(64 * kWaves) void fthe_horner192_kernel(const uint32_t *x, uint64_t stride, uint32_t planes,
+                                                                     uint32_t sq, uint32_t *out, const uint32_t *kctx,
+                                                                     uint64_t count, uint32_t nwg) {
+    __shared__ uint32_t s_ctx[kCtxWords];                       // mu limbs, N limbs, N dwords
+    __shared__ uint32_t s_rows[kPerWg * kRowStride];
+    __shared__ uint32_t s_next;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l = lane & 7, oct = lane >> 3;
+    for (int i = tid; i < kCtxWords; i += 64 * kWaves) s_ctx[i] = kctx[i];
+    if (tid == 0) s_next = 0;
+    __syncthreads();
+    const uint32_t *s_mu = s_ctx + kMuOff / 4, *s_nl = s_ctx + kNlOff / 4, *s_nd = s_ctx + kNdOff / 4;
+    uint32_t *area = s_rows + (wave * kRowsPerWave + oct) * kRowStride;
+    const bool lane0 = l == 0, top = l == kLanes - 1;
+    const uint64_t nbatch = (count + kRowsPerWave - 1) / kRowsPerWave;
+    const uint32_t total = 1 + (planes - 1) * (sq + 1);
+    for (;;) {
+        uint32_t tk = 0;
+        if (lane == 0) tk = atomicAdd(&s_next, 1u);
+        tk = __builtin_amdgcn_readfirstlane(tk);
+        const uint64_t batch = blockIdx.x + (uint64_t)tk * nwg;
+        if (batch >= nbatch) break;
+        // the octet's row, recomputed where it is used rather than kept across the products
+        auto row_of = [&](bool &live) {
+            uint64_t row = batch * kRowsPerWave + (uint32_t)(opaque(lane) >> 3);
+            live = row < count;
+            return live ? row : count - 1;
+        };
+        uint32_t xl[kPerLane];
+        bool live;
+        {
+            uint4 v[6];
+            load_row(x + (uint64_t)(planes - 1) * stride * kWords, row_of(live), l, v);
+            stage(area, v, l);
+        }
+        wave_sync();
+        // u: squarings done since the last row; j: the plane whose row is multiplied next
+        uint32_t u = 0, j = planes - 2;
+#pragma unroll 1
+        for (uint32_t s = 0; s < total; s++) {
+            if (s && u < sq) {
+                u++;
+                column_of(area, l, xl);
+            } else {
+                if (s) {
+                    uint4 v[6];
+                    load_row(x + (uint64_t)j * stride * kWords, row_of(live), l, v);
+                    stage(area, v, l);             // over the spent high limbs of the step before
+                    wave_sync();
+                    u = 0;
+                    j--;
+                }
+                limbs_of(area, l, xl);
+                wave_sync();
+                if (s == 0) {
+#pragma unroll
+                    for (int i = 0; i < kPerLane; i++) area[kPerLane * l + i] = (lane0 && i == 0) ? 1u : 0u;
+                }
+            }
+            wave_sync();
+            product<kFull>(xl, area, area, lane0, top);
+            barrett(xl, area, s_mu, s_nl, l, lane0, top);
+        }
+        uint32_t r[24];
+        canonical_dwords(area, s_nd, l, lane0, r);
+        const uint64_t row = row_of(live);
+        if (live) store_row(out, row, l, r);
+        wave_sync();
+    }
+}
+
 }  // namespace
+
+int launch_horner(hipStream_t st, const uint32_t *x, size_t stride, int planes, int sq, uint32_t *out, const void *kctx,
+                  size_t count, int n_cu) {
+    if (count == 0) return hipSuccess;
+    if (planes < 2 || sq < 1 || stride < count) return hipErrorInvalidValue;
+    const uint64_t products = horner_products(planes, sq);
+    const size_t per = std::min<size_t>((size_t)pow_blocks(count, n_cu) * kPerWg *
+                                            (size_t)std::max<uint64_t>(1, kPowBudget / products),
+                                        (size_t)1 << 22);
+    for (size_t off = 0; off < count; off += per) {
+        const size_t cnt = std::min(per, count - off);
+        const unsigned blocks = pow_blocks(cnt, n_cu);
+        hipLaunchKernelGGL(fthe_horner192_kernel, dim3(blocks), dim3(64 * kWaves), 0, st, x + off * kWords,
+                           (uint64_t)stride, (uint32_t)planes, (uint32_t)sq, out + off * kWords, (const uint32_t *)kctx,
+                           (uint64_t)cnt, blocks);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
 
 int launch_inv_up(hipStream_t st, const uint32_t *x, uint32_t *pre, uint32_t *dst, const void *kctx, size_t count,
                   int n_cu) {

@@ -124,6 +124,17 @@ int launch_pow(hipStream_t st, const uint32_t *x, int xw, const uint32_t *t, uin
                const uint32_t *sched, uint32_t slen, unsigned entries, uint64_t products, uint32_t *table, int w,
                size_t count, int n_cu);
 
+// ---- fthe_horner192: out[i] = prod_{j < planes} x[j stride + i]^(2^(j sq)) mod N ----
+// Horner from the top plane: the seed by 1, then per plane below it sq squarings and a product by its row.  Restates
+// tools/mul192_model.py horner_products().
+inline uint64_t horner_products(int planes, int sq) { return 1 + (uint64_t)(planes - 1) * ((uint64_t)sq + 1); }
+
+// One call: count output rows, planes >= 2 and sq >= 1 the same for all of them, plane j's rows at x + j stride rows
+// (stride >= count), in launches cut by launch_pow's rule (kPowBudget products per wave, 2^22 rows).  Rows of 192
+// words, any value; out canonical, not overlapping x.  No scratch.  Returns a hipError_t.
+int launch_horner(hipStream_t st, const uint32_t *x, size_t stride, int planes, int sq, uint32_t *out, const void *kctx,
+                  size_t count, int n_cu);
+
 // ---- fthe_inv192_up / fthe_inv192_down: the batched inverse as a radix-8 tree ----
 // Level 0 is the call's count rows; level l + 1 has one row per group of 8 rows of level l, the group's product; the
 // first level of at most 8 rows is the top, inverted on the host.  Restates tools/mul192_model.py inverse_levels() /

@@ -111,7 +111,20 @@ void  fthe_host_free(void *p);
  * on a public key, or a key holder's with FTHE_ENC_PUBLIC, without the fixed-base flags; r injected (r_words of
  * 1..96, zero-extended) or drawn on the device exactly as at the other sizes (same stream, same index0), in chunks
  * of 65,536 rows whose r (chunk x 384 B) lies in the scratch behind the tables.  The host add and the host encrypts
- * are staged in chunks of 65,536 rows (FTHE_MUL192_CHUNK overrides, read per call).  The gathered 8-way product of such rows runs on a second kernel of
+ * are staged in chunks of 65,536 rows (FTHE_MUL192_CHUNK overrides, read per call).  The packed and slot-packed
+ * pairs take the same path:
+ *     fthe_encrypt_gh_packed[_dev], fthe_encrypt_gh_slots[_dev]
+ * encrypt their plaintext words (6, or slots x slot_bits / 32 <= 96: 13 slots of 224 bits) as fthe_encrypt_words
+ * does, r, r_words, rng_seed and index0 as fthe_encrypt_u64_at; the fixed-base flags stay FTHE_ERR_UNSUPPORTED on
+ * that path, and so does fthe_encrypt_shared.  The key holder's fthe_decrypt_gh_packed[_dev] and
+ * fthe_decrypt_gh_slots[_dev], full and short, are the CRT decrypt of the other sizes.
+ *     fthe_compress_gh_slots[_dev]
+ * runs on a sixth kernel of that file (fthe_horner192: an octet of lanes owns an output row and walks its planes
+ * from the top, slot_bits squarings and one product per plane, the running value resident in LDS; one launch set
+ * for the rows with J planes and one for those with J - 1, a lone plane copied), 1 + (P - 1)(slot_bits + 1)
+ * products for a row of P planes, which is what fthe_last_montmuls sums.  The device form needs no scratch; the
+ * host form stages FTHE_MUL192_CHUNK output rows at a time, a chunk's planes (at most 13 x chunk x 768 B) and its
+ * rows through the context's buffers.  out overlaps no input.  The gathered 8-way product of such rows runs on a second kernel of
  * that file (fthe_gprod192: the running product stays in LDS between a group's members), and with it
  *     fthe_reduce_segments[_dev], fthe_reduce_segments_csr_dev, fthe_reduce_segments_zero_first_dev,
  *     fthe_histogram_dev, fthe_histogram_zero_first_dev, fthe_scan_segments[_dev]
@@ -140,8 +153,8 @@ void  fthe_host_free(void *p);
  * fthe_last_montmuls / fthe_last_kernel_ms count these calls' products and time.
  * Every other call that works mod n^2 returns FTHE_ERR_UNSUPPORTED for such a key: fthe_sub, fthe_sub_bits,
  * fthe_scalar_mul_rows, fthe_dot_segments, the
- * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the packed and slot-packed pair
- * calls, the public-key encrypt with a fixed-base flag, and fthe_add_shared / fthe_scalar_mul_u64_shared /
+ * Montgomery-resident rows (fthe_to_mont / fthe_from_mont / fthe_add_mont), the public-key encrypt with a
+ * fixed-base flag (the packed and slot-packed forms included), and fthe_add_shared / fthe_scalar_mul_u64_shared /
  * fthe_encrypt_shared on the public path.  A key holder's CRT encrypt
  * and decrypt at this size run mod p^2, q^2 as before; they are not part of this paragraph's claim.
  * n of 2049..3040 bits stays FTHE_ERR_UNSUPPORTED.

@@ -24,7 +24,8 @@ borrow or when that bit (limb 227, bit 15) is set.
 chain() is the gathered product of fthe_gprod192 (one lazy factor per product), power() the sliding-window walk of
 fthe_pow192 (both factors lazy) with its schedule builder: schedule(), products(), plan().  inverse() is the radix-8
 tree of fthe_inv192_up / fthe_inv192_down with its count and workspace formulas: inverse_levels(),
-inverse_products(), inverse_blocks(), inverse_ws_bytes().
+inverse_products(), inverse_blocks(), inverse_ws_bytes().  horner() is the walk over planes of fthe_horner192
+(DESIGN.md 27), horner_products() its count.
 
 Run:  python tools/mul192_model.py [seed] [trials]
 """
@@ -427,6 +428,43 @@ def power(x, e, n, t=None, w=None, lanes=False, count=None, observer=None):
     return row
 
 
+def horner_products(planes, sq):
+    """products of one row of fthe_horner192: the seed by 1, then sq squarings and a product per plane below the top"""
+    return 1 + (planes - 1) * (sq + 1)
+
+
+def horner(xs, sq, n, lanes=False, count=None, observer=None):
+    """prod_j xs[j]^(2^(j sq)) mod n^2 as fthe_horner192 forms one output row: xs the row's planes from
+    plane 0 up, any rows of 192 words, sq >= 1.  A lone plane is the device copy of its row: no product, the row as it
+    is (a row >= N stays so).  Else Horner from the top plane: the seed xs[-1] times the column 1, then per plane below
+    it sq squarings of the multiplier column and one product by that plane's row.  The seed and the rows are below
+    2^6144, the column after the seed a lazy remainder below 2N <= 2^6145: every product is power()'s case, whose
+    bounds lazy_product() asserts.  count: a list that receives the number of products run.  observer:
+    lazy_product()'s.  Returns the canonical result."""
+    assert n_ok(n) and sq >= 1 and xs and all(0 <= v < 1 << (32 * WORDS) for v in xs)
+    N = n * n
+    ran = [0]
+    if len(xs) == 1:
+        if count is not None:
+            count.append(0)
+        return xs[0]
+
+    def step(xl, r):
+        return lazy_product(xl, r, N, lanes, ran, observer)
+
+    r = step(xs[-1], 1)
+    for x in reversed(xs[:-1]):
+        for _ in range(sq):
+            r = step(r, r)
+        r = step(x, r)
+    assert ran[0] == horner_products(len(xs), sq)
+    if count is not None:
+        count.append(ran[0])
+    row = canonical(r, N, observer)
+    assert row == reduce_mod([pow(x, 1 << (j * sq), N) for j, x in enumerate(xs)], N)
+    return row
+
+
 def main():
     seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
     trials = int(sys.argv[2]) if len(sys.argv) > 2 else 20
@@ -442,6 +480,7 @@ def main():
         power(rng.getrandbits(32 * WORDS), rng.getrandbits(12) | 2, n, w=3, lanes=trials <= 4)
         N = n * n
         inverse(N, [top // N * N - 1, N - 1, 2, 1] * 3, a=[top] * 12, offset=1, n=n)
+        horner([top, rng.getrandbits(32 * WORDS), top], 3, n, lanes=trials <= 4)
     print("mul192 model: ok")
 
 
